@@ -1,8 +1,8 @@
 #!/usr/bin/env python
 """bench.py — throughput of the MI355X BEVFusion hot path on synthetic nuScenes-shaped frames.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B | --global-batch G] [--no-cpu-baseline]
-                    [--spconv-dtype fp16|fp32|bf16] [--feat-dtype fp32|bf16] [--dry-run]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B | --global-batch G] [--full [--no-cpu-baseline] [--no-extras]]
+                    [--spconv-dtype fp16|fp32|bf16] [--feat-dtype fp32|bf16] [--dump-outputs DIR] [--dry-run]
 
 `--gpus N` with no launcher environment (WORLD_SIZE unset) re-executes this file under `torch.distributed.run` with N ranks on
 127.0.0.1, one rank per GPU (RCCL); under a launcher it uses the ranks it was given.  `--dry-run` swaps the GPU work for a
@@ -19,8 +19,10 @@ sizes, inputs already resident in HBM:
 One process per GPU; for N>1 the driver launches this file under torch.distributed.run and ranks meet only in
 barriers (the path shards by frame: no data-path collective, weak scaling).
 
-Prints ONE JSON line on rank 0 with `roofline` for the dominant kernel (bev_pool scatter, HBM-bound) and
-`cpu_baseline` (reference algorithms on the host cores, bounded sample).
+Prints ONE JSON line on rank 0 with `roofline` for the dominant kernel (bev_pool scatter, HBM-bound).  A plain run only sets up,
+warms up, times the K steps and prints the line; `--full` adds every secondary measurement after the timed region: the roofline
+kernel solo, `cpu_baseline` (reference algorithms on the host cores, bounded sample), `extra`, `roofline_spconv` and the uncached
+plan costs.  `--dump-outputs DIR` writes what the last timed step computed as .npy files.
 """
 import argparse
 import json
@@ -102,14 +104,28 @@ def parse():
                          "per step, frustum geometry + pooling plan + column plan rebuilt INSIDE the timed step, point clouds rotating through a "
                          "pool; static = round 5's protocol (one test-time calibration, plan built once outside the timed loop, the same clouds)")
     ap.add_argument("--no-extras", action="store_true",
-                    help="infer mode, one rank: skip the secondary measurements of `extra` (bev_pool on bf16 features = BASELINE "
+                    help="with --full, infer mode, one rank: skip the secondary measurements of `extra` (bev_pool on bf16 features = BASELINE "
                          "configs[1], the single-frame step, the product step without the double-counted API kernel, 5 steps of "
                          "--mode train-step --amp at 4 frames = configs[4]); they run AFTER the timed region and add ~20 s")
+    ap.add_argument("--full", action="store_true",
+                    help="infer mode: besides the timed steps, run every secondary measurement — the CPU baseline and `extra` (each "
+                         "unless its --no-* flag is given), the per-layer convolution profile with its GEMM yardstick (roofline_spconv), "
+                         "the roofline kernel solo after the timed region, the uncached plan / geometry costs and the eager LiDAR "
+                         "sub-timings.  Without it a run sets up, warms up, times --steps steps and prints the line; its roofline "
+                         "figure is then the bev_pool launch inside the timed steps")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (rank 0) as DIR/<name>.npy in float32 / "
+                         "float64: whole arrays up to 2^21 elements, larger ones as a fixed seeded sample of 2^21 elements (sorted "
+                         "flat indices drawn with seed 0), at most 64 MB in all.  Inputs are seeded: the same arguments give the "
+                         "same inputs on every run")
     ap.add_argument("--cpu-baseline-worker", default=None, help=argparse.SUPPRESS)   # internal: child process of cpu_baseline()
     ap.add_argument("--dry-run", action="store_true",
                     help="no GPU: a host stub stands in for the hot path and gloo for RCCL, everything else (launch, sharding, "
                          "barriers, timing, JSON) is the real code path")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def respawn_under_launcher(args):
@@ -375,6 +391,23 @@ def emit(res):
             except OSError:
                 pass
     print(compact_line(res, side), flush=True)
+
+
+DUMP_ELEMS = 1 << 21   # per array: 8 MB in float32; the step's largest outputs (330 MB each at 8 frames) are sampled to this
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: each tensor of {name: tensor} -> out_dir/<name>.npy, floating point as float32, integers as float64.
+    A tensor of more than DUMP_ELEMS elements is reduced ON THE DEVICE to the elements at DUMP_ELEMS sorted flat indices drawn
+    with a fixed seed from its element count: the same positions on every run, so two builds compare element for element."""
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in arrays.items():
+        flat = t.detach().reshape(-1)
+        if flat.numel() > DUMP_ELEMS:
+            idx = torch.randint(flat.numel(), (DUMP_ELEMS,), generator=torch.Generator().manual_seed(0)).sort().values
+            flat = flat[idx.to(flat.device)]
+        flat = flat.float() if flat.is_floating_point() else flat.double()
+        np.save(os.path.join(out_dir, name + ".npy"), flat.cpu().numpy())
 
 
 def box_info(dev_index=0):
@@ -773,6 +806,7 @@ def train_step(args, rank, world, frame_ids, dev):
     coors_order = "linear" if args.voxel_order == "key" else None
     names = ["geometry+plan", "bev_pool_fwd", "bev_pool_bwd", "fused_pool_fwd", "fused_pool_bwd", "voxelize", "encoder_fwd", "encoder_bwd+allreduce",
              "clip+adamw"]
+    last_step = max(1, args.warmup) + args.steps - 1          # index of the last timed step: its results are kept for --dump-outputs
 
     def step(ev=None):
         mark = (lambda i: ev[i].record()) if ev else (lambda i: None)
@@ -824,6 +858,9 @@ def train_step(args, rank, world, frame_ids, dev):
             torch.nn.utils.clip_grad_norm_(enc.parameters(), 35.0)
             opt.step()
         opt.zero_grad(set_to_none=True)
+        if args.dump_outputs and i == last_step:      # references only: no device work added to the step
+            state["outputs"] = dict(bev_pool=out, fused_pool=outf, encoder_out=y, feats_grad=feats.grad, depth_grad=depth.grad,
+                                    ctx_grad=ctx.grad)
         feats.grad = depth.grad = ctx.grad = None
         mark(9)
         if augmented and ev is None:        # warm-up steps only (untimed): which fused kernel the step's plan selects, runs per image column
@@ -845,6 +882,9 @@ def train_step(args, rank, world, frame_ids, dev):
         torch.cuda.synchronize()
         barrier()
         elapsed_local = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        params = torch.cat([p.detach().reshape(-1).float() for p in enc.parameters()])      # the weights the step updated
+        dump_outputs(args.dump_outputs, dict(state.pop("outputs"), encoder_params=params))
     elapsed = max_over_ranks(elapsed_local, device=dev)
     frames_per_step = int(sum_over_ranks(B, device=dev))
     stage = {n: float(np.mean([e[i].elapsed_time(e[i + 1]) for e in evs])) for i, n in enumerate(names)}
@@ -984,7 +1024,8 @@ def main():
     gen = torch.Generator(device=dev).manual_seed(1234 + rank)
     feats = torch.randn((geom.shape[0], C), generator=gen, device=dev, dtype=torch.float32)
     n_cam = cfg["num_cameras"]
-    inp["feats"] = feats[: geom.shape[0] // B].cpu().numpy() if (rank == 0 and world == 1 and not args.no_cpu_baseline) else None   # frame 0: the CPU baseline's sample
+    cpu_base = args.full and rank == 0 and world == 1 and not args.no_cpu_baseline
+    inp["feats"] = feats[: geom.shape[0] // B].cpu().numpy() if cpu_base else None   # frame 0: the CPU baseline's sample
     if args.feat_dtype == "bf16":
         feats = feats.bfloat16()
     elem = feats.element_size()
@@ -1000,11 +1041,13 @@ def main():
     plan = BevPoolPlan.from_geometry(geom, B, inp["origin"], inp["dx"], inp["nx"], want_intervals=True)
     torch.cuda.synchronize()
     t_first = time.perf_counter() - t0
-    t0 = time.perf_counter()
-    for _ in range(5):
-        plan = BevPoolPlan.from_geometry(geom, B, inp["origin"], inp["dx"], inp["nx"], want_intervals=True)
-    torch.cuda.synchronize()
-    precompute_ms = (time.perf_counter() - t0) / 5 * 1e3
+    precompute_ms = None
+    if args.full:
+        t0 = time.perf_counter()
+        for _ in range(5):
+            plan = BevPoolPlan.from_geometry(geom, B, inp["origin"], inp["dx"], inp["nx"], want_intervals=True)
+        torch.cuda.synchronize()
+        precompute_ms = (time.perf_counter() - t0) / 5 * 1e3
     n_kept, n_int = plan.n_kept(), plan.n_intervals()
     bev = torch.empty((B, D, H, W, C), dtype=torch.float32, device=dev)
 
@@ -1033,23 +1076,25 @@ def main():
     torch.cuda.synchronize()
     if sp_dtype != torch.float32 and enc.last_path != "fused":
         raise SystemExit(f"bench: the SparseEncoder left its sync-free fused path ({enc.last_path_reason})")
-    state["probe"] = True
-    sub = []
-    for _ in range(5):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        _, _, mid = lidar_branch()
-        b.record()
-        b.synchronize()
-        sub.append((a.elapsed_time(mid), mid.elapsed_time(b)))
-    state["probe"] = False
-    eager_vox_ms, eager_enc_ms = (float(np.median([t[i] for t in sub])) for i in (0, 1))
+    eager_vox_ms = eager_enc_ms = None
+    if args.full:
+        state["probe"] = True
+        sub = []
+        for _ in range(5):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            _, _, mid = lidar_branch()
+            b.record()
+            b.synchronize()
+            sub.append((a.elapsed_time(mid), mid.elapsed_time(b)))
+        state["probe"] = False
+        eager_vox_ms, eager_enc_ms = (float(np.median([t[i] for t in sub])) for i in (0, 1))
 
     # per-layer convolution figures (`roofline_spconv`): one eager pass with HIP events around every layer
     from bevfusion_amd.spconv import fused as _fused
 
     roofline_spconv = None
-    if sp_dtype != torch.float32:
+    if args.full and sp_dtype != torch.float32:
         _fused.LAYER_PROFILE = []
         _fused.LAYER_PROFILE_REPS = 5    # 5 back-to-back launches per layer between the events (a single launch behind a sync runs down-clocked)
         try:
@@ -1238,14 +1283,16 @@ def main():
                                  extra_rots=t_la[:, :3, :3], extra_trans=t_la[:, :3, 3])
             return vt.make_plan(gm, B)
 
-    for _ in range(2):
-        camera_geometry_uncached()
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    for _ in range(5):
-        camera_geometry_uncached()
-    torch.cuda.synchronize()
-    geometry_plan_ms = (time.perf_counter() - t0) / 5 * 1e3
+    geometry_plan_ms = None
+    if args.full:
+        for _ in range(2):
+            camera_geometry_uncached()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(5):
+            camera_geometry_uncached()
+        torch.cuda.synchronize()
+        geometry_plan_ms = (time.perf_counter() - t0) / 5 * 1e3
 
     STAGES = ["depth_raster", "fused_depth_context_pool", "bev_pool_forward_cells",
               "voxelize_mean + sparse_encoder" if not overlap_head else
@@ -1447,6 +1494,9 @@ def main():
     stage_ms = [float(np.mean([e[s].elapsed_time(e[s + 1]) for e in evs])) for s in range(NSTAGE)]
     state["n_voxels"] = int(state["n_voxels_dev"].reshape(-1)[0])
     assert tuple(state["lidar_bev"].shape) == (B, 256, 180, 180)
+    if args.dump_outputs and rank == 0:   # before anything after the timed region launches into the same buffers
+        dump_outputs(args.dump_outputs, dict(depth_raster=state["depth_img"], fused_pool=fused_out, bev_pool=bev,
+                                             lidar_bev=state["lidar_bev"], n_voxels=state["n_voxels_dev"]))
     if overlap_pipe or bev_pool_alone:   # report in the canonical order (raster, fused pooling, bev_pool, LiDAR)
         stage_ms = [stage_ms[1], stage_ms[2], stage_ms[0], stage_ms[3]]
     kern_ms = stage_ms[2]  # the bev_pool stage is exactly one kernel launch
@@ -1505,10 +1555,10 @@ def main():
         ev[n].synchronize()
         return sum(ev[i].elapsed_time(ev[i + 1]) for i in range(n)) / n
 
-    solo_b2b_ms = kernel_ms(lambda: plan.launch_forward(feats, bev), n=20, warm=2) if shared else None
-    solo_ms = kernel_duration_ms(lambda: plan.launch_forward(feats, bev)) if shared else None
+    solo_b2b_ms = kernel_ms(lambda: plan.launch_forward(feats, bev), n=20, warm=2) if shared and args.full else None
+    solo_ms = kernel_duration_ms(lambda: plan.launch_forward(feats, bev)) if shared and args.full else None
 
-    if rank == 0 and world == 1 and not args.no_extras and ((args.overlap == "none" and graph is not None) or overlap_voxel or overlap_chain or overlap_lidar or overlap_ahead):
+    if args.full and rank == 0 and world == 1 and not args.no_extras and ((args.overlap == "none" and graph is not None) or overlap_voxel or overlap_chain or overlap_lidar or overlap_ahead):
         extra = {}
         t_extra = time.perf_counter()
         # (iv) the product's step: what a deployment runs per batch — raster + fused pooling + LiDAR branch — without the API-level
@@ -1760,7 +1810,7 @@ def main():
             import copy
 
             a2 = copy.copy(args)
-            a2.amp, a2.steps, a2.warmup, a2.global_batch = True, 5, 2, 0
+            a2.amp, a2.steps, a2.warmup, a2.global_batch, a2.dump_outputs = True, 5, 2, 0, None
             tr = train_step(a2, 0, 1, list(range(4)), dev)
             extra["train_step_amp"] = dict(ms_per_step=tr["ms_per_step"], frames_per_s=tr["value"], frames=4, steps=5,
                                            stage_ms=tr["config"]["stage_ms"], bev_pool_bwd_frac=tr["roofline"]["frac"],
@@ -1903,6 +1953,8 @@ def main():
                 "measured": ("solo: mean duration of 20 launches after the timed region, one HIP event pair around EACH (as a kernel "
                              "trace measures; rocprof_kernel_us: the stored trace); kernel_ms_in_step: with the LiDAR streams beside it "
                              "(extra.alone_frac_in_step: first and alone in the step)") if solo_ms is not None else
+                            ("in the step: HIP events around the one launch of every timed step, with the LiDAR streams beside it "
+                             "(--full adds the solo figure)") if shared else
                             "in the step: HIP events around the one launch of every timed step, nothing beside it",
             },
         }
@@ -1914,7 +1966,7 @@ def main():
                                     "kernel_ms": bf["kernel_ms"], "kernel_ms_back_to_back": bf.get("kernel_ms_back_to_back"),
                                     "measured": "solo, right after the timed region: average duration of 20 launches, one HIP event pair around each"}
         res["box"] = box_sampled
-        if not args.no_cpu_baseline and world == 1:
+        if cpu_base:
             res["cpu_baseline"] = cpu_baseline(inp, pts_np, cfg, B, D, H, W)
         else:
             res["cpu_baseline"] = None

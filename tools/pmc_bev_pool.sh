@@ -3,14 +3,16 @@
 # (kernel-trace only, no other trace domain), over the default bench command.
 tag=${1:-x}
 export TMPDIR=/tmp
-out=$GRAFT_REPO_ROOT/gpurun_out/pmc_bev_$tag
+REPO=$(cd "$(dirname "$0")/.." && pwd)
+OUT=$(mkdir -p "${OUT:?set OUT to the directory the artefacts go to}" && cd "$OUT" && pwd)
+out=$OUT/pmc_bev_$tag
 rm -rf $out; mkdir -p $out
 cd /tmp
 for c in FETCH_SIZE WRITE_SIZE; do
-  timeout 300 rocprofv3 --kernel-trace --output-format csv --pmc $c -d $out/$c -o r -- python $GRAFT_REPO_ROOT/bench.py --steps 5 --warmup 2 --no-cpu-baseline > $out/${c}_run.log 2>&1
+  timeout 300 rocprofv3 --kernel-trace --output-format csv --pmc $c -d $out/$c -o r -- python "$REPO"/bench.py --steps 5 --warmup 2 --full --no-cpu-baseline > $out/${c}_run.log 2>&1
   echo "$c rc=$?"
 done
-cd $GRAFT_REPO_ROOT
+cd "$REPO"
 python - <<PY
 import csv, glob, collections
 acc = collections.defaultdict(lambda: collections.defaultdict(list))
