@@ -58,6 +58,9 @@ _SIGNATURES = {
     "bevamd_depth_raster": (I, [P, I, I, P, P, P, P, I, I, I, P, P, Z, P]),
     "bevamd_depth_raster_batch": (I, [P, P, I, I, P, P, I, P, P, I, I, I, P, P, Z, P]),
     "bevamd_depth_raster_batch_zero_ws": (I, [P, P, I, I, P, P, I, P, P, I, I, I, P, P, Z, P]),
+    "bevamd_depth_inputs_channels": (I, [I, I, I, I]),
+    "bevamd_depth_inputs_batch": (I, [P, P, I, I, P, P, I, P, P, I, I, I, I, I, I, I, P, P, Z, P]),
+    "bevamd_depth_inputs_batch_zero_ws": (I, [P, P, I, I, P, P, I, P, P, I, I, I, I, I, I, I, P, P, Z, P]),
     "bevamd_lss_geometry": (I, [P, I, P, P, P, P, P, P, I, I, P, P]),
     "bevamd_mat3_inverse": (I, [P, LL, LL, I, P, P]),
     "bevamd_mat3_inverse_with_column": (I, [P, LL, LL, I, P, P, P]),

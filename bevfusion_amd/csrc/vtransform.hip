@@ -75,10 +75,9 @@ struct RasterArgs {
   int n, nfeat, ncam, ih, iw;
 };
 
-// pixel (row, col) and depth of point i in camera c; false if it falls outside the image
-__device__ __forceinline__ bool project(const RasterArgs& a, int i, int c, int& row, int& col, float& dist) {
-  const float* p = a.points + (size_t)i * a.nfeat;
-  float x = p[0] - a.aug_trans[0], y = p[1] - a.aug_trans[1], z = p[2] - a.aug_trans[2];
+// pixel (row, col) and depth of the point (px, py, pz) in camera c; false if it falls outside the image
+__device__ __forceinline__ bool project_xyz(const RasterArgs& a, float px, float py, float pz, int c, int& row, int& col, float& dist) {
+  float x = px - a.aug_trans[0], y = py - a.aug_trans[1], z = pz - a.aug_trans[2];
   float u, v, w;
   mat3_apply(load_mat3(a.aug_inv_rot, 3), x, y, z, u, v, w);
   const float* l2i = a.lidar2image + (size_t)c * 16;
@@ -96,6 +95,10 @@ __device__ __forceinline__ bool project(const RasterArgs& a, int i, int c, int& 
   row = (int)v;
   col = (int)u;
   return true;
+}
+__device__ __forceinline__ bool project(const RasterArgs& a, int i, int c, int& row, int& col, float& dist) {
+  const float* p = a.points + (size_t)i * a.nfeat;
+  return project_xyz(a, p[0], p[1], p[2], c, row, col, dist);
 }
 
 // Collisions resolve to the LAST point in input order (deterministic; the reference's GPU index_put is unordered).  One pass: a
@@ -191,6 +194,114 @@ __global__ __launch_bounds__(256) void depth_raster_batch_points_kernel(RasterBa
     float dist;
     if (project(a, i, c, row, col, dist))
       atomicMax(&packed[(((size_t)b * a.ncam + c) * a.ih + row) * a.iw + col], raster_pack(i, dist));
+  }
+}
+
+// ---- depth inputs: every option of BaseDepthTransform.forward (base.py:266-329) --------------------------------------------
+// depth_input 'scalar' | 'one-hot', height_expand, add_depth_features -> depth [B, ncam, Cd, ih, iw], Cd = (1 | D) + (F | 0).
+// Three launches per <= RASTER_MAX_BATCH samples, in this order on one stream:
+//   1. depth_inputs_zero_planes_kernel  the planes that are zero except where a point lands — all Cd of them (one-hot) or the F feature
+//                                       planes (scalar) — streamed out with 16-byte stores along iw: this fill IS the cost of the op;
+//   2. depth_inputs_scatter_kernel      one thread per VIRTUAL point (height_expand: stored point v >> 3 at height 0.25 * ((v & 7) + 1),
+//                                       built in registers — the 8x cloud of base.py:269-273 never exists), walking the cameras like
+//                                       depth_raster_batch_points_kernel: the 64-bit maximum on the winner map (scalar plane / feature
+//                                       planes wanted) and, one-hot, a plain store of 1.0f into the bin plane (every writer of a word
+//                                       writes the same value; ordered after launch 1 by the stream);
+//   3. depth_inputs_winners_kernel      one pass over the map: the scalar depth plane (dense) and, at the pixels a point won, the F
+//                                       values of its row; clears the map words it read, like depth_raster_unpack_clear_kernel.
+// (A pixel pass that wrote the feature planes whole, zeros included, with 16-byte stores ran at 4 TB/s against the fill's 6.2: 18 + 1
+// write streams per workgroup instead of one.  Hit pixels are a few percent of an image, so their words are written twice instead.)
+// Every word of the output is written by launch 1 or launch 3: no fill of the output from the caller.
+#define BEVAMD_DEPTH_SCALAR 0    // mirrored in include/bevfusion_amd.h
+#define BEVAMD_DEPTH_ONE_HOT 1
+struct DepthInputs {
+  int num_bins;   // 0: scalar mode (plane 0 = depth of the winner); D: one-hot mode (planes 0..D-1)
+  int expand;     // 1: height_expand
+  int nplanes;    // Cd
+  int nfeat_out;  // F with add_depth_features, else 0
+};
+
+__device__ __forceinline__ unsigned long long raster_pack_virtual(unsigned v, float dist) {
+  return ((unsigned long long)(v + 1u) << 32) | (unsigned long long)__float_as_uint(dist);
+}
+
+__global__ __launch_bounds__(256) void depth_inputs_zero_planes_kernel(float* __restrict__ depth, size_t span_stride, size_t span_len) {
+  float* base = depth + (size_t)blockIdx.y * span_stride;
+  size_t head = (size_t)((4u - (unsigned)(((uintptr_t)base >> 2) & 3u)) & 3u);   // floats up to the next 16-byte boundary
+  if (head > span_len) head = span_len;
+  const size_t nvec = (span_len - head) >> 2;
+  float4* v = (float4*)(base + head);
+  const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
+  const size_t j0 = (size_t)blockIdx.x * 512 + threadIdx.x;   // a workgroup zeroes 8 KiB in a row
+  if (j0 < nvec) v[j0] = zero;
+  if (j0 + 256 < nvec) v[j0 + 256] = zero;
+  if (blockIdx.x == 0) {   // <= 3 floats in front of the first and behind the last 16-byte word
+    const size_t tail = span_len - head - (nvec << 2);
+    if (threadIdx.x < head) base[threadIdx.x] = 0.f;
+    if (threadIdx.x < tail) base[head + (nvec << 2) + threadIdx.x] = 0.f;
+  }
+}
+
+__global__ __launch_bounds__(256) void depth_inputs_scatter_kernel(RasterBatch rb, DepthInputs di, unsigned long long* __restrict__ packed,
+                                                                   float* __restrict__ depth) {
+  const int b = blockIdx.y;
+  const unsigned v = blockIdx.x * 256u + threadIdx.x;
+  const unsigned nv = di.expand ? (unsigned)rb.n[b] * 8u : (unsigned)rb.n[b];
+  if (v >= nv) return;
+  RasterArgs a;
+  a.points = rb.points[b];
+  a.aug_inv_rot = rb.aug_inv_rot + (size_t)b * 9;
+  a.aug_trans = rb.aug_trans + (size_t)b * rb.trans_stride;
+  a.lidar2image = rb.lidar2image + (size_t)b * rb.ncam * 16;
+  a.img_aug = rb.img_aug + (size_t)b * rb.ncam * 16;
+  a.n = rb.n[b]; a.nfeat = rb.nfeat; a.ncam = rb.ncam; a.ih = rb.ih; a.iw = rb.iw;
+  const float* p = a.points + (size_t)(di.expand ? v >> 3 : v) * a.nfeat;
+  const float px = p[0], py = p[1], pz = di.expand ? 0.25f * (float)((v & 7u) + 1u) : p[2];
+  const size_t plane = (size_t)a.ih * a.iw;
+  for (int c = 0; c < rb.ncam; ++c) {
+    int row, col;
+    float dist;
+    if (!project_xyz(a, px, py, pz, c, row, col, dist)) continue;
+    const size_t cam = (size_t)b * a.ncam + c, pix = (size_t)row * a.iw + col;
+    if (packed) atomicMax(&packed[cam * plane + pix], raster_pack_virtual(v, dist));
+    if (di.num_bins) {   // bin = the metric distance truncated (base.py:325-326), dist >= 1e-5
+      int bin = (int)fminf(dist, (float)(di.num_bins - 1));
+      bin = bin < 0 ? 0 : (bin >= di.num_bins ? di.num_bins - 1 : bin);
+      depth[(cam * di.nplanes + bin) * plane + pix] = 1.0f;
+    }
+  }
+}
+
+// feature f of the row the reference finds at virtual point v when it writes the planes: its in-place `cur_coords -= translation`
+// (base.py:290) has already changed x, y, z (with height_expand z is the replaced height), the other columns are copies
+// (a word whose index lies outside the cloud — a map that was not zero when the call started — reads nothing)
+__device__ __forceinline__ float depth_inputs_feature(const float* __restrict__ pts, const float* __restrict__ trans, int nfeat, int expand,
+                                                      unsigned nv, unsigned long long w, int f) {
+  const unsigned v = (unsigned)(w >> 32) - 1u;
+  if (v >= nv) return 0.f;
+  const float* p = pts + (size_t)(expand ? v >> 3 : v) * nfeat;
+  if (f >= 3) return p[f];
+  const float x = (f == 2 && expand) ? 0.25f * (float)((v & 7u) + 1u) : p[f];
+  return x - trans[f];
+}
+
+__global__ __launch_bounds__(256) void depth_inputs_winners_kernel(RasterBatch rb, DepthInputs di, unsigned long long* __restrict__ packed,
+                                                                   float* __restrict__ depth) {
+  const int bc = blockIdx.y, b = bc / rb.ncam;
+  const size_t plane = (size_t)rb.ih * rb.iw;
+  unsigned long long* map = packed + (size_t)bc * plane;
+  float* out = depth + ((size_t)bc * di.nplanes + di.num_bins) * plane;   // the scalar plane (scalar mode), then the F feature planes
+  const float* __restrict__ pts = rb.points[b];
+  const float* __restrict__ trans = rb.aug_trans + (size_t)b * rb.trans_stride;
+  const int scalar = di.num_bins == 0 ? 1 : 0;
+  const unsigned nv = di.expand ? (unsigned)rb.n[b] * 8u : (unsigned)rb.n[b];
+  for (size_t p = (size_t)blockIdx.x * 256 + threadIdx.x; p < plane; p += (size_t)gridDim.x * 256) {
+    const unsigned long long w = map[p];
+    if (scalar) out[p] = __uint_as_float((unsigned)(w & 0xFFFFFFFFull));   // dense, like depth_raster_unpack_clear_kernel
+    if (!w) continue;
+    map[p] = 0ull;
+    float* fo = out + (size_t)scalar * plane + p;
+    for (int f = 0; f < di.nfeat_out; ++f) fo[(size_t)f * plane] = depth_inputs_feature(pts, trans, rb.nfeat, di.expand, nv, w, f);
   }
 }
 
@@ -414,6 +525,103 @@ static int depth_raster_batch(const float* const* points, const int* num_points,
   else depth_raster_unpack_kernel<<<dim3((unsigned)(ub < 8192 ? ub : 8192)), dim3(256), 0, stream>>>(packed, npix, depth);
   BEVAMD_LAUNCH_CHECK("depth_raster_unpack");
   return BEVAMD_OK;
+}
+
+/* Every option of BaseDepthTransform.forward's depth input (base.py:266-329) for a whole batch; see the kernels above. */
+static int depth_inputs_batch(const float* const* points, const int* num_points, int batch, int num_features,
+                              const float* lidar_aug_inv_rot, const float* lidar_aug_trans, int trans_stride, const float* lidar2image,
+                              const float* img_aug, int ncam, int ih, int iw, int depth_mode, int num_bins, int height_expand,
+                              int add_features, float* depth, void* ws, size_t ws_bytes, void* stream_, bool ws_is_zero) {
+  hipStream_t stream = (hipStream_t)stream_;
+  BEVAMD_REQUIRE(batch > 0 && num_features >= 3 && ncam > 0 && ncam <= 4095 && ih > 0 && iw > 0 && trans_stride >= 3,
+                 "depth_inputs_batch: bad sizes");
+  BEVAMD_REQUIRE(depth_mode == BEVAMD_DEPTH_SCALAR || depth_mode == BEVAMD_DEPTH_ONE_HOT, "depth_inputs_batch: depth_mode %d is neither scalar (0) nor one-hot (1)", depth_mode);
+  BEVAMD_REQUIRE(depth_mode == BEVAMD_DEPTH_SCALAR || num_bins > 0, "depth_inputs_batch: one-hot needs num_bins > 0");
+  BEVAMD_REQUIRE(points && num_points && depth && lidar_aug_inv_rot && lidar_aug_trans && lidar2image && img_aug,
+                 "depth_inputs_batch: null buffer");
+  for (int b = 0; b < batch; ++b) {
+    BEVAMD_REQUIRE(num_points[b] >= 0 && (num_points[b] == 0 || points[b]), "depth_inputs_batch: bad sample %d", b);
+    // the map keeps (virtual index + 1) in 32 bits
+    BEVAMD_REQUIRE(!height_expand || 8ull * (unsigned long long)num_points[b] < 0xFFFFFFFFull, "depth_inputs_batch: sample %d has too many points for height_expand", b);
+  }
+  DepthInputs di;
+  di.num_bins = depth_mode == BEVAMD_DEPTH_ONE_HOT ? num_bins : 0;
+  di.expand = height_expand ? 1 : 0;
+  di.nfeat_out = add_features ? num_features : 0;
+  di.nplanes = (di.num_bins ? di.num_bins : 1) + di.nfeat_out;
+  const bool need_map = di.num_bins == 0 || di.nfeat_out > 0;   // one-hot bins alone have no winner
+  const size_t per = (size_t)ncam * ih * iw, plane = (size_t)ih * iw;
+  if (need_map && (!ws || ws_bytes < (size_t)batch * bevamd_depth_raster_workspace_bytes(ncam, ih, iw))) {
+    set_error("depth_inputs_batch: workspace too small");
+    return BEVAMD_ERR_WORKSPACE;
+  }
+  unsigned long long* packed = need_map ? (unsigned long long*)ws : nullptr;
+  if (need_map && !ws_is_zero) {
+    int rc = device_fill_u32((uint32_t*)packed, per * batch * 2, 0u, stream);
+    if (rc) return rc;
+  }
+  // launch 1: everything the later launches write only where a point landed — all planes (one-hot) or the feature planes (scalar)
+  const size_t zero_from = di.num_bins ? 0 : plane, zero_len = (size_t)di.nplanes * plane - zero_from;
+  for (int b0 = 0; b0 < batch; b0 += RASTER_MAX_BATCH) {
+    RasterBatch rb;
+    rb.batch = batch - b0 < RASTER_MAX_BATCH ? batch - b0 : RASTER_MAX_BATCH;
+    rb.start[0] = 0;
+    int nmax = 0;
+    for (int j = 0; j < RASTER_MAX_BATCH; ++j) {
+      rb.points[j] = j < rb.batch ? points[b0 + j] : nullptr;
+      rb.n[j] = j < rb.batch ? num_points[b0 + j] : 0;
+      rb.start[j + 1] = 0;   // unused here: the kernels take the sample from blockIdx.y
+      nmax = rb.n[j] > nmax ? rb.n[j] : nmax;
+    }
+    rb.aug_inv_rot = lidar_aug_inv_rot + (size_t)b0 * 9;
+    rb.aug_trans = lidar_aug_trans + (size_t)b0 * trans_stride;
+    rb.lidar2image = lidar2image + (size_t)b0 * ncam * 16;
+    rb.img_aug = img_aug + (size_t)b0 * ncam * 16;
+    rb.nfeat = num_features; rb.ncam = ncam; rb.ih = ih; rb.iw = iw; rb.trans_stride = trans_stride;
+    float* out = depth + (size_t)b0 * ncam * di.nplanes * plane;
+    unsigned long long* map = packed ? packed + (size_t)b0 * per : nullptr;
+    if (zero_len) {
+      const size_t blocks = (zero_len / 4 + 511) / 512;   // two 16-byte stores per thread
+      BEVAMD_REQUIRE(blocks < (1ull << 31), "depth_inputs_batch: too many planes");
+      depth_inputs_zero_planes_kernel<<<dim3((unsigned)(blocks < 1 ? 1 : blocks), rb.batch * ncam), dim3(256), 0, stream>>>(
+          out + zero_from, (size_t)di.nplanes * plane, zero_len);
+      BEVAMD_LAUNCH_CHECK("depth_inputs_zero_planes");
+    }
+    if (nmax > 0) {
+      const long long nvmax = (long long)nmax * (di.expand ? 8 : 1);
+      depth_inputs_scatter_kernel<<<dim3(cdiv(nvmax, 256), rb.batch), dim3(256), 0, stream>>>(rb, di, map, out);
+      BEVAMD_LAUNCH_CHECK("depth_inputs_scatter");
+    }
+    if (need_map) {
+      const size_t wb = (plane + 255) / 256;
+      depth_inputs_winners_kernel<<<dim3((unsigned)(wb < 65536 ? wb : 65536), rb.batch * ncam), dim3(256), 0, stream>>>(rb, di, map, out);
+      BEVAMD_LAUNCH_CHECK("depth_inputs_winners");
+    }
+  }
+  return BEVAMD_OK;
+}
+
+int bevamd_depth_inputs_batch(const float* const* points, const int* num_points, int batch, int num_features,
+                              const float* lidar_aug_inv_rot, const float* lidar_aug_trans, int trans_stride, const float* lidar2image,
+                              const float* img_aug, int ncam, int ih, int iw, int depth_mode, int num_bins, int height_expand,
+                              int add_features, float* depth, void* ws, size_t ws_bytes, void* stream_) {
+  return depth_inputs_batch(points, num_points, batch, num_features, lidar_aug_inv_rot, lidar_aug_trans, trans_stride, lidar2image, img_aug,
+                            ncam, ih, iw, depth_mode, num_bins, height_expand, add_features, depth, ws, ws_bytes, stream_, false);
+}
+
+int bevamd_depth_inputs_batch_zero_ws(const float* const* points, const int* num_points, int batch, int num_features,
+                                      const float* lidar_aug_inv_rot, const float* lidar_aug_trans, int trans_stride,
+                                      const float* lidar2image, const float* img_aug, int ncam, int ih, int iw, int depth_mode,
+                                      int num_bins, int height_expand, int add_features, float* depth, void* ws, size_t ws_bytes,
+                                      void* stream_) {
+  return depth_inputs_batch(points, num_points, batch, num_features, lidar_aug_inv_rot, lidar_aug_trans, trans_stride, lidar2image, img_aug,
+                            ncam, ih, iw, depth_mode, num_bins, height_expand, add_features, depth, ws, ws_bytes, stream_, true);
+}
+
+int bevamd_depth_inputs_channels(int depth_mode, int num_bins, int num_features, int add_features) {
+  if ((depth_mode != BEVAMD_DEPTH_SCALAR && depth_mode != BEVAMD_DEPTH_ONE_HOT) || num_features < 3) return 0;
+  if (depth_mode == BEVAMD_DEPTH_ONE_HOT && num_bins <= 0) return 0;
+  return (depth_mode == BEVAMD_DEPTH_ONE_HOT ? num_bins : 1) + (add_features ? num_features : 0);
 }
 
 int bevamd_lss_geometry(const float* frustum, int frustum_points, const float* post_rot_inv, const float* post_trans,

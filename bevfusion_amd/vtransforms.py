@@ -316,15 +316,21 @@ class BaseTransform(nn.Module):
 
 class BaseDepthTransform(BaseTransform):
     def depth_raster(self, img, points, lidar2image, img_aug_matrix, lidar_aug_matrix):
-        """base.py:269-329 for depth_input='scalar' without extra features: project every LiDAR point into every
-        camera and write its range at the truncated pixel -> [B, N, 1, iH, iW].  One scatter per sample for all
-        cameras (the reference loops over cameras with boolean indexing); colliding points are last-writer-wins
-        in both."""
+        """base.py:269-329: project every point into every camera and write, at the truncated pixel, what the module's
+        options ask for -> [B, N, Cd, iH, iW], Cd = (1 | D) + (F if add_depth_features else 0):
+          depth_input 'scalar'   channel 0 = range of the last point in input order that lands there;
+          depth_input 'one-hot'  channels 0..D-1: every hit sets bin `int(min(range, D - 1))` to 1;
+          height_expand          every point stands for 8 points at heights 0.25 .. 2.0;
+          add_depth_features     the last F channels = the winning point's row (x, y, z less the LiDAR-augmentation translation).
+        One scatter per sample for all cameras (the reference loops over cameras with boolean indexing).  Unlike the
+        reference, the caller's point tensors and list are left as they were."""
         batch_size = len(points)
         n_cam = img.shape[1]
         iH, iW = self.image_size
         if points[0].is_cuda:
             return self._depth_raster_native(points, n_cam, lidar2image, img_aug_matrix, lidar_aug_matrix)
+        if self.depth_input != "scalar" or self.height_expand or self.add_depth_features:
+            return self._depth_inputs_host(points, n_cam, lidar2image, img_aug_matrix, lidar_aug_matrix)
         depth = torch.zeros(batch_size, n_cam, 1, iH, iW, device=points[0].device)
         for b in range(batch_size):
             cur_coords = points[b][:, :3].float()
@@ -355,15 +361,73 @@ class BaseDepthTransform(BaseTransform):
             depth[b].view(-1)[lin[on_img]] = dist[on_img]
         return depth
 
+    def _depth_inputs_host(self, points, n_cam, lidar2image, img_aug_matrix, lidar_aug_matrix):
+        """Host tensors, every option: the reference's arithmetic (base.py:269-329) on copies of the points.  Collisions are
+        resolved explicitly — the winner of a pixel is the largest (virtual) point index that lands on it, what the
+        reference's sequential assignment leaves — so the result does not depend on the number of threads."""
+        iH, iW = self.image_size
+        one_hot = self.depth_input == "one-hot"
+        n_bins = self.D if one_hot else 1
+        nfeat = points[0].shape[1]
+        n_ch = n_bins + (nfeat if self.add_depth_features else 0)
+        depth = torch.zeros(len(points), n_cam, n_ch, iH, iW, device=points[0].device)
+        for b in range(len(points)):
+            rows = points[b].float()
+            if self.height_expand:                                     # base.py:269-273
+                rows = rows.repeat_interleave(8, dim=0)
+                rows[:, 2] = torch.arange(0.25, 2.25, 0.25).repeat(points[b].shape[0])
+            elif rows is points[b]:
+                rows = rows.clone()
+            cur_img_aug_matrix = img_aug_matrix[b].float()
+            cur_lidar_aug_matrix = lidar_aug_matrix[b].float()
+            cur_lidar2image = lidar2image[b].float()
+            cur_coords = rows[:, :3]
+            cur_coords -= cur_lidar_aug_matrix[:3, 3]                  # in place on OUR copy: the rows the feature planes show
+            cur_coords = torch.inverse(cur_lidar_aug_matrix[:3, :3]).contiguous().matmul(cur_coords.transpose(1, 0))
+            cur_coords = cur_lidar2image[:, :3, :3].matmul(cur_coords)
+            cur_coords += cur_lidar2image[:, :3, 3].reshape(-1, 3, 1)
+            dist = cur_coords[:, 2, :]
+            cur_coords[:, 2, :] = torch.clamp(cur_coords[:, 2, :], 1e-5, 1e5)
+            cur_coords[:, :2, :] /= cur_coords[:, 2:3, :]
+            cur_coords = cur_img_aug_matrix[:, :3, :3].matmul(cur_coords)
+            cur_coords += cur_img_aug_matrix[:, :3, 3].reshape(-1, 3, 1)
+            cur_coords = cur_coords[:, :2, :].transpose(1, 2)
+            cur_coords = cur_coords[..., [1, 0]]  # (row, col)
+            on_img = ((cur_coords[..., 0] < iH) & (cur_coords[..., 0] >= 0) & (cur_coords[..., 1] < iW)
+                      & (cur_coords[..., 1] >= 0))
+            pix = cur_coords.long()
+            cam, idx = on_img.nonzero(as_tuple=True)                   # hits, camera-major, point index ascending
+            lin = (cam * iH + pix[cam, idx, 0]) * iW + pix[cam, idx, 1]
+            hit_dist = dist[cam, idx]
+            out = depth[b].view(n_cam, n_ch, iH * iW)
+            if one_hot:
+                bins = torch.clamp(hit_dist, max=self.D - 1).long()    # base.py:325-326
+                out[cam, bins, lin - cam * (iH * iW)] = 1.0
+            if not one_hot or self.add_depth_features:
+                winner = torch.full((n_cam * iH * iW,), -1, dtype=torch.long)
+                winner.scatter_reduce_(0, lin, idx, "amax")
+                won = winner[lin] == idx                               # one hit per pixel
+                cam, idx, lin, hit_dist = cam[won], idx[won], lin[won] - cam[won] * (iH * iW), hit_dist[won]
+                if not one_hot:
+                    out[cam, 0, lin] = hit_dist
+                if self.add_depth_features:
+                    out[cam, n_bins:, lin] = rows[idx]
+        return depth
+
     def _depth_raster_native(self, points, n_cam, lidar2image, img_aug_matrix, lidar_aug_matrix):
         """csrc/vtransform.hip: one (packed atomicMax, unpack) kernel pair for the whole batch, all cameras at once, no host sync; a pixel hit
         by several points keeps the LAST one in input order (the reference's assignment order on CPU; its GPU
-        index_put is unordered)."""
+        index_put is unordered).  With one-hot bins, height expansion or feature planes: `bevamd_depth_inputs_batch_zero_ws` (zeroed
+        planes, scatter of the virtual points, one pass over the map for the winners' planes) over the same persistent map."""
         lib = _capi.load()
         iH, iW = self.image_size
         dev = points[0].device
         B = len(points)
-        depth = torch.empty((B, n_cam, 1, iH, iW), dtype=torch.float32, device=dev)
+        plain = self.depth_input == "scalar" and not self.height_expand and not self.add_depth_features
+        one_hot = self.depth_input == "one-hot"
+        nfeat = points[0].shape[1]
+        n_ch = 1 if plain else (self.D if one_hot else 1) + (nfeat if self.add_depth_features else 0)
+        depth = torch.empty((B, n_cam, n_ch, iH, iW), dtype=torch.float32, device=dev)
         if self.lapack_inverse:
             trans = lidar_aug_matrix[:, :3, 3].float().contiguous()
             inv_rot = torch.inverse(lidar_aug_matrix[:, :3, :3].float()).contiguous()
@@ -382,6 +446,14 @@ class BaseDepthTransform(BaseTransform):
             raise RuntimeError("depth_raster: every sample must have the same number of point features")
         ptrs = (ctypes.c_void_p * B)(*[p.data_ptr() for p in pts])
         counts = (ctypes.c_int * B)(*[int(p.shape[0]) for p in pts])
+        if not plain:
+            mode = (1 if one_hot else 0, self.D if one_hot else 0, int(bool(self.height_expand)), int(bool(self.add_depth_features)))
+        if not plain and one_hot and not self.add_depth_features:      # bins alone: no winner, no map
+            with torch.cuda.device(dev):
+                rc = lib.bevamd_depth_inputs_batch(ptrs, counts, B, nfeat, _capi.ptr(inv_rot), _capi.ptr(trans), 3, _capi.ptr(l2i),
+                                                   _capi.ptr(ia), n_cam, iH, iW, *mode, _capi.ptr(depth), None, 0, _capi.stream_ptr(dev))
+            _capi.check(rc, "depth_inputs_batch")
+            return depth
         with torch.cuda.device(dev):
             wsb = lib.bevamd_depth_raster_workspace_bytes(n_cam, iH, iW) * B
             # one zero-initialised (winner, depth) map per device and size, left zero by every raster (the unpack pass clears what
@@ -395,7 +467,16 @@ class BaseDepthTransform(BaseTransform):
                 while len(_RASTER_MAPS) >= _RASTER_MAPS_MAX:      # bounded (69 MB per map at 8 frames, one per stream ever used):
                     _RASTER_MAPS.pop(next(iter(_RASTER_MAPS)))    # the oldest goes; a stream that comes back takes a fresh, zeroed map
                 ws = _RASTER_MAPS[key] = torch.zeros(wsb, dtype=torch.uint8, device=dev)
-            if ws is not None:
+            if not plain:
+                persistent = ws is not None
+                if not persistent:
+                    ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
+                fn = lib.bevamd_depth_inputs_batch_zero_ws if persistent else lib.bevamd_depth_inputs_batch
+                rc = fn(ptrs, counts, B, nfeat, _capi.ptr(inv_rot), _capi.ptr(trans), 3, _capi.ptr(l2i), _capi.ptr(ia), n_cam, iH, iW,
+                        *mode, _capi.ptr(depth), _capi.ptr(ws), wsb, _capi.stream_ptr(dev))
+                if rc != 0 and persistent:
+                    _RASTER_MAPS.pop(key, None)
+            elif ws is not None:
                 rc = lib.bevamd_depth_raster_batch_zero_ws(ptrs, counts, B, nfeat, _capi.ptr(inv_rot), _capi.ptr(trans), 3,
                                                            _capi.ptr(l2i), _capi.ptr(ia), n_cam, iH, iW, _capi.ptr(depth),
                                                            _capi.ptr(ws), wsb, _capi.stream_ptr(dev))
@@ -416,9 +497,6 @@ class BaseDepthTransform(BaseTransform):
             sensor2ego, lidar2ego, cam_intrinsic, camera2lidar, img_aug_matrix, lidar_aug_matrix)
         if self.use_points == "radar":
             points = radar
-        if self.height_expand or self.add_depth_features or self.depth_input != "scalar":
-            raise NotImplementedError("only scalar 1-channel depth input is implemented (what DepthLSSTransform's "
-                                      "Conv2d(1, 8, 1) stem and the released checkpoint use; SURVEY.md D3)")
         depth = self.depth_raster(img, points, lidar2image, img_aug_matrix, lidar_aug_matrix)
         geom = self._geometry_or_cached(c2l_rots, c2l_trans, intrins, post_rots, post_trans, extra_rots, extra_trans,
                                         kwargs.get("calibration_id"))

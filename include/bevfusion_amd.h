@@ -259,6 +259,38 @@ int bevamd_depth_raster_batch_zero_ws(const float* const* points, const int* num
                                       const float* lidar2image, const float* img_aug, int ncam, int ih, int iw, float* depth,
                                       void* ws, size_t ws_bytes, void* stream);
 
+/* The depth INPUT of BaseDepthTransform.forward with every option of the reference (base.py:266-329), for a whole batch and without
+ * a host sync; arguments up to iw as bevamd_depth_raster_batch.  depth [batch, ncam, Cd, ih, iw] fp32 is fully written (zeros where
+ * nothing lands), Cd = bevamd_depth_inputs_channels(...) = (1 | num_bins) + (num_features if add_features else 0):
+ *   depth_mode BEVAMD_DEPTH_SCALAR   plane 0 = clamped depth of the LAST point in input order that hits the pixel (num_bins ignored);
+ *   depth_mode BEVAMD_DEPTH_ONE_HOT  planes 0..num_bins-1: EVERY hit sets plane (int)min(depth, num_bins - 1) to 1.0 (the metric
+ *                                    depth truncated, base.py:325-326);
+ *   height_expand != 0               every point counts as 8 consecutive points, copies of its row with z = 0.25, 0.50 .. 2.00
+ *                                    (base.py:269-273; generated in registers, the 8x cloud is never stored; 8 * num_points[b] must stay
+ *                                    below 2^32 - 1);
+ *   add_features != 0                the last num_features planes hold the whole row of the winning (last in input order) point as the
+ *                                    reference sees it there: x, y, z minus lidar_aug_trans (z the replaced height under height_expand),
+ *                                    the other columns copied.
+ * The caller's points are not modified (the reference overwrites them).  ws: batch * bevamd_depth_raster_workspace_bytes(ncam, ih, iw),
+ * needed (and touched) only when a winner is: scalar mode or add_features; it may be NULL for one-hot planes alone.  ncam <= 4095.
+ * The _zero_ws form takes a PERSISTENT map like bevamd_depth_raster_batch_zero_ws: all zero when the call starts; both forms leave
+ * the map all zero once their kernels have run.  Per 16 samples: the planes that are zero except where a point lands streamed out
+ * (all of them in one-hot mode, the feature planes in scalar mode), scatter, winners pass over the map (when a winner is needed) —
+ * 3 launches at most; the first form adds the fill of the map.  No fill of `depth` by the caller. */
+#define BEVAMD_DEPTH_SCALAR 0
+#define BEVAMD_DEPTH_ONE_HOT 1
+int bevamd_depth_inputs_channels(int depth_mode, int num_bins, int num_features, int add_features);   /* Cd; 0 for invalid arguments */
+int bevamd_depth_inputs_batch(const float* const* points, const int* num_points, int batch, int num_features,
+                              const float* lidar_aug_inv_rot, const float* lidar_aug_trans, int trans_stride,
+                              const float* lidar2image, const float* img_aug, int ncam, int ih, int iw, int depth_mode,
+                              int num_bins, int height_expand, int add_features, float* depth, void* ws, size_t ws_bytes,
+                              void* stream);
+int bevamd_depth_inputs_batch_zero_ws(const float* const* points, const int* num_points, int batch, int num_features,
+                                      const float* lidar_aug_inv_rot, const float* lidar_aug_trans, int trans_stride,
+                                      const float* lidar2image, const float* img_aug, int ncam, int ih, int iw, int depth_mode,
+                                      int num_bins, int height_expand, int add_features, float* depth, void* ws, size_t ws_bytes,
+                                      void* stream);
+
 /* Replaces BaseTransform.get_geometry (base.py:92-135): frustum [frustum_points, 3] (u, v, d) -> geom
  * [batch*cams, frustum_points, 3] in the lidar frame.  post_rot_inv [batch*cams,3,3] = inverse(img_aug[:3,:3]),
  * post_trans [batch*cams,3], combine [batch*cams,3,3] = camera2lidar_rot @ inverse(intrinsics), camera2lidar_trans
