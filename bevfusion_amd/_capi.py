@@ -157,6 +157,11 @@ _EXT_SIGNATURES = {
     "bevamd_dynamic_scatter_backward": (I, [P, P, P, P, P, P, I, I, I, I, P, P]),
     "bevamd_spconv_maxpool_forward": (I, [P, I, I, P, I, I, I, I, P, I, P]),
     "bevamd_spconv_maxpool_backward": (I, [P, P, P, I, P, I, I, I, I, P, P]),
+    # pillar / radar encoders
+    "bevamd_pillar_decorate": (I, [P, P, P, I, I, I, I, I, P, P, P]),
+    "bevamd_pillar_stack_forward": (I, [P, P, P, I, I, I, I, I, P, I, P, P, P, P, P, P]),
+    "bevamd_pillar_scatter_forward": (I, [P, I, P, I, I, I, I, I, P, P, P]),
+    "bevamd_pillar_scatter_backward": (I, [P, I, P, P, I, I, I, I, I, P, P]),
 }
 
 

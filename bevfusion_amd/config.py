@@ -99,9 +99,10 @@ def load_config(path, root=None, evaluate=True):
 
 
 def build_hot_path(cfg):
-    """Instantiate the hot-path modules a BEVFusion config names: the camera view transform and the LiDAR
-    voxelizer + sparse backbone (fusion_models/bevfusion.py:36-69).  Returns a dict with whatever is present."""
-    from . import sparse_encoder, vtransforms  # noqa: F401  (registration side effects)
+    """Instantiate the hot-path modules a BEVFusion config names: the camera view transform, the LiDAR voxelizer + backbone
+    (sparse encoder or pillar encoder) and the radar voxelizer + backbone (fusion_models/bevfusion.py:36-69).  Returns a
+    dict with whatever is present."""
+    from . import pillar_encoder, sparse_encoder, vtransforms  # noqa: F401  (registration side effects)
     from .registry import BACKBONES, VTRANSFORMS
     from .voxel import Voxelization
 
@@ -118,4 +119,12 @@ def build_hot_path(cfg):
             out["voxelize_reduce"] = lid.get("voxelize_reduce", True)
         if lid["backbone"]["type"] in BACKBONES:
             out["lidar_backbone"] = BACKBONES.build(lid["backbone"])
+    rad = enc.get("radar")
+    if rad:
+        v = dict(rad["voxelize"])
+        if v.get("max_num_points", -1) > 0:
+            out["radar_voxelize"] = Voxelization(**v)
+            out["radar_voxelize_reduce"] = rad.get("voxelize_reduce", True)
+        if rad["backbone"]["type"] in BACKBONES:
+            out["radar_backbone"] = BACKBONES.build(rad["backbone"])
     return out

@@ -58,6 +58,46 @@ int bevamd_spconv_maxpool_backward(const void* features, const void* out_feature
                                    const int* nbr_t, int nbr_t_stride, int num_in, int kernel_volume, int channels,
                                    void* in_grad, void* stream);
 
+
+/* Pillar / radar encoders.  Replace PillarFeatureNet / RadarFeatureNet / PointPillarsScatter of
+ *   mmdet3d/models/backbones/pillar_encoder.py and radar_encoder.py.
+ * Common inputs: voxels [num_pillars, max_points, num_features] fp32, num_points [num_pillars] int32, coors [num_pillars, 4]
+ *   int32 ordered (b, x, y, z); mode 0 = pillar, 1 = radar; geom: HOST array of 10 floats
+ *   {vx, vy, x_offset, y_offset, lo_x, lo_y, lo_z, hi_x - lo_x, hi_y - lo_y, hi_z - lo_z}, each computed in double the way
+ *   the reference's constructor does and rounded once to fp32.
+ * bevamd_pillar_decorate: out [num_pillars, max_points, F_out].
+ *   pillar: F_out = F + 5 (+ 1 with_distance): [features, xyz - sum_over_P(xyz) / num_points, x - (float(cx) * vx + x_offset),
+ *           y - (float(cy) * vy + y_offset), (|xyz|)]; every row p >= num_points is multiplied by 0.
+ *   radar : F_out = F + 2: [features with xyz replaced by (v - lo) / (hi - lo), f_center from the un-normalised x, y]; the same
+ *           mask, then nan_to_num (NaN -> 0, +-inf -> +-FLT_MAX).  with_distance is ignored.
+ *   No FMA contraction: every column but f_cluster is bit-equal to the reference's fp32 arithmetic.
+ * bevamd_pillar_stack_forward: the eval-mode network in one launch: decorate, then per layer l Linear without bias
+ *   (weights[l]: DEVICE [K_l, units_l] fp32 — the Linear weight TRANSPOSED) -> folded BatchNorm (scales[l], shifts[l]: DEVICE
+ *   [units_l]) -> ReLU -> combine: pillar non-last [x, max_over_P(x)], radar non-last x, last max_over_P(x); out
+ *   [num_pillars, units_last] fp32.  The max runs over all P rows: the padded rows (all equal) are computed once per pillar.
+ *   units / weights / scales / shifts are HOST arrays of num_layers entries.  Limits: at most 4 layers, units multiples of 4 up
+ *   to 128 (pillar non-last: up to 64), num_features up to 64, max_points up to 32; anything else returns 4 (unsupported)
+ *   before any GPU work.  num_points is clamped to [0, max_points] for the row count.
+ * bevamd_pillar_scatter_forward: canvas [batch_size, channels, nx, ny] (dtype 0 fp32, 1 fp16) with
+ *   canvas[b, c, x * ny + y] = feats[row, c], zero elsewhere; the whole canvas is written.  winner: int32
+ *   [batch_size, nx * ny] scratch that the call resets itself and leaves holding the winning row of every cell (-1: empty) for
+ *   the backward.  Duplicated cells: the highest row wins; rows with b outside [0, batch_size) or x / y outside the canvas
+ *   are dropped.
+ * bevamd_pillar_scatter_backward: grad_feats [num_pillars, channels] = grad_canvas[b, :, cell] for the winner of a cell, 0 for
+ *   every other row.
+ * No device synchronisation, no float atomics: results are bit-reproducible. */
+int bevamd_pillar_decorate(const float* voxels, const int* num_points, const int* coors, int num_pillars, int max_points,
+                           int num_features, int mode, int with_distance, const float* geom, float* out, void* stream);
+int bevamd_pillar_stack_forward(const float* voxels, const int* num_points, const int* coors, int num_pillars,
+                                int max_points, int num_features, int mode, int with_distance, const float* geom,
+                                int num_layers, const int* units, const void* const* weights, const void* const* scales,
+                                const void* const* shifts, float* out, void* stream);
+int bevamd_pillar_scatter_forward(const void* feats, int dtype, const int* coors, int num_pillars, int channels,
+                                  int batch_size, int nx, int ny, int* winner, void* canvas, void* stream);
+int bevamd_pillar_scatter_backward(const void* grad_canvas, int dtype, const int* coors, const int* winner,
+                                   int num_pillars, int channels, int batch_size, int nx, int ny, void* grad_feats,
+                                   void* stream);
+
 #ifdef __cplusplus
 }
 #endif
