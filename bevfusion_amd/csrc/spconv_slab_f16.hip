@@ -115,35 +115,28 @@ int bevamd_spconv_conv_forward_slab(const void* features, int dtype, int feat_st
                                     const float* bn_scale, const float* bn_shift, const void* residual,
                                     int residual_stride, int relu, int variant, void* stream_) {
   hipStream_t stream = (hipStream_t)stream_;
-  BEVAMD_REQUIRE(dtype == tile::T_F16 || dtype == tile::T_BF16, "spconv_conv_forward_slab: dtype %d is not 16-bit", dtype);
+  static const char* const name = "spconv_conv_forward_slab";
+  // every slab kernel reads rows (the filter-stationary ones the residual too) through buffer descriptors, whose size field has 32 bits
+  static const tile::FeatureLimit limit = {0x100000000ull, "", "the feature tensor must be smaller than 4 GiB (buffer descriptor)"};
   const bool narrow = cin >= 1 && cin <= 16 && (cout == 16 || cout == 32) && (cout == 16 || cin > 8);
-  BEVAMD_REQUIRE(narrow || (cin == cout && (cin == 32 || cin == 64 || cin == 128)), "spconv_conv_forward_slab: %d -> %d channels", cin, cout);
   const int cinp = narrow ? (cin <= 8 ? 8 : 16) : cin;
-  BEVAMD_REQUIRE(num_out >= 0 && num_in >= 0, "spconv_conv_forward_slab: bad sizes");
-  if (num_out == 0) return BEVAMD_OK;
-  BEVAMD_REQUIRE(features && image && hdr && slots && out, "spconv_conv_forward_slab: null buffer");
-  BEVAMD_REQUIRE(block_rows == bevamd_spconv_slab_block_rows(cin, variant),
-                 "spconv_conv_forward_slab: metadata built for %d-row blocks, variant %d wants %d", block_rows, variant,
-                 bevamd_spconv_slab_block_rows(cin, variant));
-  BEVAMD_REQUIRE(feat_stride >= cinp && feat_stride % 8 == 0 && ((uintptr_t)features & 15) == 0,
-                 "spconv_conv_forward_slab: feature pitch %d must be a multiple of 8 and >= %d, 16-byte aligned", feat_stride, cinp);
-  BEVAMD_REQUIRE((unsigned long long)num_in * (unsigned long long)feat_stride * 2ull < 0x100000000ull,
-                 "spconv_conv_forward_slab: the feature tensor must be smaller than 4 GiB (buffer descriptor)");
-  BEVAMD_REQUIRE(!residual || (unsigned long long)num_out * (unsigned long long)residual_stride * 2ull < 0x100000000ull,
-                 "spconv_conv_forward_slab: the residual tensor must be smaller than 4 GiB (buffer descriptor)");
-  BEVAMD_REQUIRE(((uintptr_t)image & 15) == 0 && ((uintptr_t)slots & 15) == 0, "spconv_conv_forward_slab: image / slots must be 16-byte aligned");
-  BEVAMD_REQUIRE(out_stride >= cout && (!residual || residual_stride >= cout), "spconv_conv_forward_slab: bad output pitch");
-  BEVAMD_REQUIRE((bn_scale == nullptr) == (bn_shift == nullptr), "spconv_conv_forward_slab: scale and shift go together");
-  slab::SlabArgs sa;
-  tile::Args& a = sa.a;
-  a.hdr = nullptr; a.slots = nullptr; a.slab_rows = 0;   // (the slab kernels read sa.hdr / sa.slots)
-  a.feat = features; a.wimg = image; a.nbr = nullptr; a.m_dev = num_out_dev; a.out = out;
-  a.bias = bias; a.scale = bn_scale; a.shift = bn_shift; a.residual = residual;
-  a.feat_stride = feat_stride; a.n_in = num_in; a.nbr_stride = 0; a.m_cap = num_out; a.K = 27;
-  a.cout = cout; a.out_stride = out_stride; a.res_stride = residual_stride; a.relu = relu;
-  a.row_epilogue = cout % 8 == 0 && out_stride % 8 == 0 && ((uintptr_t)out & 15) == 0 &&
-                   (!residual || (residual_stride % 8 == 0 && ((uintptr_t)residual & 15) == 0)) &&
-                   (!bias || ((uintptr_t)bias & 15) == 0) && (!bn_scale || (((uintptr_t)bn_scale | (uintptr_t)bn_shift) & 15) == 0);
+  const tile::ConvIO io = {features, dtype, feat_stride, num_in, image, out, out_stride, bias, bn_scale, bn_shift,
+                           residual, residual_stride, relu, num_out, num_out_dev, cin, cout, cinp};
+  slab::SlabArgs sa;   // (the slab kernels read sa.hdr / sa.slots; sa.a's rulebook fields stay empty)
+  const int rc = tile::conv_args(name, io, hdr && slots, limit, [&](tile::ConvStage at) {
+    if (at == tile::AFTER_DTYPE)
+      BEVAMD_REQUIRE(narrow || (cin == cout && (cin == 32 || cin == 64 || cin == 128)), "%s: %d -> %d channels", name, cin, cout);
+    if (at == tile::AFTER_BUFFERS)
+      BEVAMD_REQUIRE(block_rows == bevamd_spconv_slab_block_rows(cin, variant), "%s: metadata built for %d-row blocks, variant %d wants %d",
+                     name, block_rows, variant, bevamd_spconv_slab_block_rows(cin, variant));
+    if (at == tile::AFTER_LIMIT) {
+      BEVAMD_REQUIRE(!residual || (unsigned long long)num_out * (unsigned long long)residual_stride * 2ull < limit.bytes,
+                     "%s: the residual tensor must be smaller than 4 GiB (buffer descriptor)", name);
+      BEVAMD_REQUIRE(((uintptr_t)image & 15) == 0 && ((uintptr_t)slots & 15) == 0, "%s: image / slots must be 16-byte aligned", name);
+    }
+    return BEVAMD_OK;
+  }, sa.a);
+  if (rc != BEVAMD_OK || num_out == 0) return rc;
   sa.hdr = (const int2*)hdr;
   sa.slots = (const uint16_t*)slots;
   sa.wimg_bytes = (unsigned)(tile::image_elems(27, cinp, cout / 16) * 2);

@@ -74,18 +74,41 @@ static inline int resident_per_xcd(PerDevice& pd, K kern, int threads, int bytes
   return pd.wg_per_xcd[dev];
 }
 
+static inline int launch_status(const char* name) {   // BEVAMD_LAUNCH_CHECK with a name that is not a literal
+  const hipError_t e = hipGetLastError();
+  if (e == hipSuccess) return BEVAMD_OK;
+  set_error("launch %s: %s", name, hipGetErrorString(e));
+  return BEVAMD_ERR_HIP;
+}
+// The two ways a slab kernel is launched.  KERN keys the template, so `pd` (a function attribute and an occupancy, both per
+// function) is one per kernel instantiation.
+// one block per tile of `block_rows` rows, rounded up to a multiple of 8 (whole rounds over the XCDs)
+template <auto KERN>
+static int launch_per_tile(const SlabArgs& sa, int threads, int lds_bytes, int block_rows, const char* name, hipStream_t stream) {
+  static PerDevice pd = {};
+  raise_lds_limit(pd, KERN, lds_bytes);
+  const long long nblk = ((long long)sa.a.m_cap + block_rows - 1) / block_rows;
+  KERN<<<dim3((unsigned)((nblk + 7) / 8 * 8)), dim3(threads), lds_bytes, stream>>>(sa);
+  return launch_status(name);
+}
+// a persistent grid: as many workgroups as stay resident (times BEVAMD_SLAB_GRID_PCT), fewer when there are fewer tiles
+template <auto KERN>
+static int launch_persistent(const SlabArgs& sa, int threads, int lds_bytes, int block_rows, const char* name, hipStream_t stream) {
+  static PerDevice pd = {};
+  const int wg_per_xcd = resident_per_xcd(pd, KERN, threads, lds_bytes);
+  if (wg_per_xcd <= 0) { set_error("spconv slab: occupancy query failed"); return BEVAMD_ERR_HIP; }
+  const long long nblk = ((long long)sa.a.m_cap + block_rows - 1) / block_rows;
+  long long gx = (nblk + 7) / 8;
+  if (gx > persistent_cap(wg_per_xcd)) gx = persistent_cap(wg_per_xcd);
+  KERN<<<dim3((unsigned)(gx * 8)), dim3(threads), lds_bytes, stream>>>(sa);
+  return launch_status(name);
+}
+
 template <int DT, int KC, int CIN, int NT, int MT, int NW, int SPS, int WR, int CAP>
 static int run(const SlabArgs& sa, hipStream_t stream) {
   typedef Plan<KC, CIN, NT, MT, NW, SPS, WR, CAP> P;
   static_assert(P::BYTES <= 160 * 1024, "LDS plan exceeds the CU");
-  auto kern = &spconv_slab_kernel<DT, KC, CIN, NT, MT, NW, SPS, WR, CAP>;
-  static PerDevice pd = {};
-  raise_lds_limit(pd, kern, P::BYTES);
-  const long long nblk = ((long long)sa.a.m_cap + P::BM - 1) / P::BM;
-  const long long blocks = (nblk + 7) / 8 * 8;
-  kern<<<dim3((unsigned)blocks), dim3(NW * 64), P::BYTES, stream>>>(sa);
-  BEVAMD_LAUNCH_CHECK("spconv_slab");
-  return BEVAMD_OK;
+  return launch_per_tile<&spconv_slab_kernel<DT, KC, CIN, NT, MT, NW, SPS, WR, CAP>>(sa, NW * 64, P::BYTES, P::BM, "spconv_slab", stream);
 }
 
 // the built configurations per input width (first entry = what variant 0 means); X(...) expands once per configuration
@@ -99,18 +122,20 @@ static int run(const SlabArgs& sa, hipStream_t stream) {
 #define BEVAMD_SLAB_SHAPES_64(X) X(64, 2, 4, 1, 3, 184) X(32, 2, 4, 1, 3, 192)
 #define BEVAMD_SLAB_SHAPES_128(X) X(64, 2, 8, 1, 3, 320) X(32, 2, 8, 3, 2, 384)
 
-static inline const Shape* shapes_of(int cin, int* n) {
-#define BEVAMD_ROW(KC, MT, NW, SPS, WR, CAP) {KC, MT, NW, SPS, WR, CAP},
-  static const Shape s32[] = {BEVAMD_SLAB_SHAPES_32(BEVAMD_ROW)};
-  static const Shape s64[] = {BEVAMD_SLAB_SHAPES_64(BEVAMD_ROW)};
-  static const Shape s128[] = {BEVAMD_SLAB_SHAPES_128(BEVAMD_ROW)};
-#undef BEVAMD_ROW
+// the shape list of an input width as a table (Shape and ShapeR: six ints a row, in the order of the X-macro's arguments)
+#define BEVAMD_ROW(A, B, C, D, E, F) {A, B, C, D, E, F},
+template <typename S, int N32, int N64, int N128>
+static inline const S* table_of(int cin, int* n, const S (&s32)[N32], const S (&s64)[N64], const S (&s128)[N128]) {
   switch (cin) {
-    case 32: *n = (int)(sizeof(s32) / sizeof(Shape)); return s32;
-    case 64: *n = (int)(sizeof(s64) / sizeof(Shape)); return s64;
-    case 128: *n = (int)(sizeof(s128) / sizeof(Shape)); return s128;
+    case 32: *n = N32; return s32;
+    case 64: *n = N64; return s64;
+    case 128: *n = N128; return s128;
     default: *n = 0; return nullptr;
   }
+}
+static inline const Shape* shapes_of(int cin, int* n) {
+  static const Shape s32[] = {BEVAMD_SLAB_SHAPES_32(BEVAMD_ROW)}, s64[] = {BEVAMD_SLAB_SHAPES_64(BEVAMD_ROW)}, s128[] = {BEVAMD_SLAB_SHAPES_128(BEVAMD_ROW)};
+  return table_of(cin, n, s32, s64, s128);
 }
 static inline int variant_code(const Shape& s) { return s.kc * 10000 + s.mt * 1000 + (s.nw / 4) * 100 + s.sps * 10 + s.wr; }
 static inline const Shape* find_shape(int cin, int variant) {
@@ -130,14 +155,7 @@ template <int DT, int KC, int CIN, int NT, int MT, int RW, int CW, int CAP, int 
 static int run_r(const SlabArgs& sa, hipStream_t stream) {
   typedef PlanR<KC, CIN, NT, MT, RW, CW, CAP> P;
   static_assert(P::BYTES <= 160 * 1024, "LDS plan exceeds the CU");
-  auto kern = &spconv_slabr_kernel<DT, KC, CIN, NT, MT, RW, CW, CAP, FLAGS>;
-  static PerDevice pd = {};
-  raise_lds_limit(pd, kern, P::BYTES);
-  const long long nblk = ((long long)sa.a.m_cap + P::BM - 1) / P::BM;
-  const long long blocks = (nblk + 7) / 8 * 8;
-  kern<<<dim3((unsigned)blocks), dim3(P::NW * 64), P::BYTES, stream>>>(sa);
-  BEVAMD_LAUNCH_CHECK("spconv_slabr");
-  return BEVAMD_OK;
+  return launch_per_tile<&spconv_slabr_kernel<DT, KC, CIN, NT, MT, RW, CW, CAP, FLAGS>>(sa, P::NW * 64, P::BYTES, P::BM, "spconv_slabr", stream);
 }
 
 // persistent flavour of the same shapes (spconv_slab_persist.h): variant = 2000000 + the same fields
@@ -145,16 +163,7 @@ template <int DT, int KC, int CIN, int NT, int MT, int RW, int CW, int CAP>
 static int run_p(const SlabArgs& sa, hipStream_t stream) {
   typedef PlanP<KC, CIN, NT, MT, RW, CW, CAP> P;
   static_assert(P::BYTES <= 160 * 1024, "LDS plan exceeds the CU");
-  auto kern = &spconv_slabp_kernel<DT, KC, CIN, NT, MT, RW, CW, CAP>;
-  static PerDevice pd = {};
-  const int wg_per_xcd = resident_per_xcd(pd, kern, P::NW * 64, P::BYTES);
-  if (wg_per_xcd <= 0) { set_error("spconv slab: occupancy query failed"); return BEVAMD_ERR_HIP; }
-  const long long nblk = ((long long)sa.a.m_cap + P::BM - 1) / P::BM;
-  long long gx = (nblk + 7) / 8;
-  if (gx > persistent_cap(wg_per_xcd)) gx = persistent_cap(wg_per_xcd);
-  kern<<<dim3((unsigned)(gx * 8)), dim3(P::NW * 64), P::BYTES, stream>>>(sa);
-  BEVAMD_LAUNCH_CHECK("spconv_slabp");
-  return BEVAMD_OK;
+  return launch_persistent<&spconv_slabp_kernel<DT, KC, CIN, NT, MT, RW, CW, CAP>>(sa, P::NW * 64, P::BYTES, P::BM, "spconv_slabp", stream);
 }
 
 #define BEVAMD_SLABR_SHAPES_32(X) X(32, 4, 4, 1, 384, 0) X(32, 2, 4, 1, 192, 0)
@@ -168,21 +177,13 @@ static int run_p(const SlabArgs& sa, hipStream_t stream) {
 #define BEVAMD_SLABR_SHAPES_128(X) X(64, 4, 2, 2, 184, 0) X(64, 4, 4, 2, 320, 0) X(64, 4, 2, 2, 184, 8) X(64, 2, 2, 2, 120, 0)
 
 static inline const ShapeR* shapes_r_of(int cin, int* n) {
-#define BEVAMD_ROW(KC, MT, RW, CW, CAP, ID) {KC, MT, RW, CW, CAP, ID},
-  static const ShapeR s32[] = {BEVAMD_SLABR_SHAPES_32(BEVAMD_ROW)};
-  static const ShapeR s64[] = {BEVAMD_SLABR_SHAPES_64(BEVAMD_ROW)};
-  static const ShapeR s128[] = {BEVAMD_SLABR_SHAPES_128(BEVAMD_ROW)};
-#undef BEVAMD_ROW
-  switch (cin) {
-    case 32: *n = (int)(sizeof(s32) / sizeof(ShapeR)); return s32;
-    case 64: *n = (int)(sizeof(s64) / sizeof(ShapeR)); return s64;
-    case 128: *n = (int)(sizeof(s128) / sizeof(ShapeR)); return s128;
-    default: *n = 0; return nullptr;
-  }
+  static const ShapeR s32[] = {BEVAMD_SLABR_SHAPES_32(BEVAMD_ROW)}, s64[] = {BEVAMD_SLABR_SHAPES_64(BEVAMD_ROW)}, s128[] = {BEVAMD_SLABR_SHAPES_128(BEVAMD_ROW)};
+  return table_of(cin, n, s32, s64, s128);
 }
+#undef BEVAMD_ROW
 constexpr int REGW_BASE = 1000000, PERSIST_BASE = 2000000;
 static inline int variant_code(const ShapeR& s) { return REGW_BASE + s.kc * 10000 + s.mt * 1000 + s.rw * 100 + s.cw * 10 + s.id; }
-static inline bool has_persistent_twin(const ShapeR& s) { return (s.id & ~3) == 0 && s.rw * 16 * s.mt != BAKED_ROWS; }
+constexpr bool has_persistent_twin(const ShapeR& s) { return (s.id & ~3) == 0 && s.rw * 16 * s.mt != BAKED_ROWS; }
 static inline const ShapeR* find_shape_r(int cin, int variant) {
   const bool persistent = variant >= PERSIST_BASE;
   if (persistent) variant -= PERSIST_BASE - REGW_BASE;   // the persistent kernels are built for the same (plain) shapes
@@ -209,16 +210,7 @@ template <int DT, int CAP>
 static int run_f(const SlabArgs& sa, hipStream_t stream) {
   typedef PlanF<CAP> P;
   static_assert(P::BYTES <= 40 * 1024, "four waves per CU: 40 KiB of LDS each");
-  auto kern = &spconv_slabf_kernel<DT, CAP>;
-  static PerDevice pd = {};
-  const int wg_per_xcd = resident_per_xcd(pd, kern, 64, P::BYTES);
-  if (wg_per_xcd <= 0) { set_error("spconv slab: occupancy query failed"); return BEVAMD_ERR_HIP; }
-  const long long nblk = ((long long)sa.a.m_cap + P::BM - 1) / P::BM;
-  long long gx = (nblk + 7) / 8;
-  if (gx > persistent_cap(wg_per_xcd)) gx = persistent_cap(wg_per_xcd);
-  kern<<<dim3((unsigned)(gx * 8)), dim3(64), P::BYTES, stream>>>(sa);
-  BEVAMD_LAUNCH_CHECK("spconv_slabf");
-  return BEVAMD_OK;
+  return launch_persistent<&spconv_slabf_kernel<DT, CAP>>(sa, 64, P::BYTES, P::BM, "spconv_slabf", stream);
 }
 // ---- filter-stationary wave pairs (spconv_slab_fstat2.h), 32 -> 32: variant = 4100000 + CAP; same metadata as 4000000 + CAP --
 constexpr int FSTAT2_BASE = 4100000;
@@ -237,16 +229,7 @@ template <int DT, int CAP>
 static int run_f2(const SlabArgs& sa, hipStream_t stream) {
   typedef PlanF2<CAP> P;
   static_assert(P::BYTES <= 53 * 1024, "three wave pairs per CU at least");
-  auto kern = &spconv_slabf2_kernel<DT, CAP>;
-  static PerDevice pd = {};
-  const int wg_per_xcd = resident_per_xcd(pd, kern, 128, P::BYTES);
-  if (wg_per_xcd <= 0) { set_error("spconv slab: occupancy query failed"); return BEVAMD_ERR_HIP; }
-  const long long nblk = ((long long)sa.a.m_cap + P::BM - 1) / P::BM;
-  long long gx = (nblk + 7) / 8;
-  if (gx > persistent_cap(wg_per_xcd)) gx = persistent_cap(wg_per_xcd);
-  kern<<<dim3((unsigned)(gx * 8)), dim3(128), P::BYTES, stream>>>(sa);
-  BEVAMD_LAUNCH_CHECK("spconv_slabf2");
-  return BEVAMD_OK;
+  return launch_persistent<&spconv_slabf2_kernel<DT, CAP>>(sa, 128, P::BYTES, P::BM, "spconv_slabf2", stream);
 }
 template <int DT>
 int launch_f_impl(const SlabArgs& sa, int cin, int nt, int variant, hipStream_t stream) {
@@ -282,16 +265,7 @@ template <int DT, int CIN, int NT, int MT, int NW, int CW, int CAP>
 static int run_s(const SlabArgs& sa, hipStream_t stream) {
   typedef PlanS<CIN, NT, MT, NW, CW, CAP> P;
   static_assert(P::BYTES <= 160 * 1024, "LDS plan exceeds the CU");
-  auto kern = &spconv_slabs_kernel<DT, CIN, NT, MT, NW, CW, CAP>;
-  static PerDevice pd = {};
-  const int wg_per_xcd = resident_per_xcd(pd, kern, NW * 64, P::BYTES);
-  if (wg_per_xcd <= 0) { set_error("spconv slab: occupancy query failed"); return BEVAMD_ERR_HIP; }
-  const long long nblk = ((long long)sa.a.m_cap + P::BM - 1) / P::BM;
-  long long gx = (nblk + 7) / 8;
-  if (gx > persistent_cap(wg_per_xcd)) gx = persistent_cap(wg_per_xcd);
-  kern<<<dim3((unsigned)(gx * 8)), dim3(NW * 64), P::BYTES, stream>>>(sa);
-  BEVAMD_LAUNCH_CHECK("spconv_slabs");
-  return BEVAMD_OK;
+  return launch_persistent<&spconv_slabs_kernel<DT, CIN, NT, MT, NW, CW, CAP>>(sa, NW * 64, P::BYTES, P::BM, "spconv_slabs", stream);
 }
 template <int DT>
 int launch_s_impl(const SlabArgs& sa, int cinp, int nt, int variant, hipStream_t stream) {
@@ -313,6 +287,11 @@ int launch_s_impl(const SlabArgs& sa, int cinp, int nt, int variant, hipStream_t
   return BEVAMD_ERR_UNSUPPORTED;
 }
 
+// the shape lists hand X six fields; BEVAMD_CASE (defined where a list is turned into kernel calls) also takes the channel width
+#define BEVAMD_WIDTH32(...) BEVAMD_CASE(32, __VA_ARGS__)
+#define BEVAMD_WIDTH64(...) BEVAMD_CASE(64, __VA_ARGS__)
+#define BEVAMD_WIDTH128(...) BEVAMD_CASE(128, __VA_ARGS__)
+
 template <int DT>
 int launch_r_impl(const SlabArgs& sa, int cin, int nt, int variant, hipStream_t stream) {
   const ShapeR* s = find_shape_r(cin, variant);
@@ -320,23 +299,14 @@ int launch_r_impl(const SlabArgs& sa, int cin, int nt, int variant, hipStream_t 
     set_error("spconv slab: no register-filter kernel for cin=%d, cout tiles=%d, variant=%d", cin, nt, variant);
     return BEVAMD_ERR_UNSUPPORTED;
   }
-#define BEVAMD_CODE(KC, MT, RW, CW, ID) (KC * 10000 + MT * 1000 + RW * 100 + CW * 10 + ID)
-#define BEVAMD_CASE32(KC, MT, RW, CW, CAP, ID)                                                                              \
-  if (cin == 32 && variant == REGW_BASE + BEVAMD_CODE(KC, MT, RW, CW, ID)) return run_r<DT, KC, 32, 2, MT, RW, CW, CAP, ((ID) & ~3)>(sa, stream); \
-  if constexpr (((ID) & ~3) == 0 && RW * 16 * MT != BAKED_ROWS) if (cin == 32 && variant == PERSIST_BASE + BEVAMD_CODE(KC, MT, RW, CW, ID)) return run_p<DT, KC, 32, 2, MT, RW, CW, CAP>(sa, stream);
-#define BEVAMD_CASE64(KC, MT, RW, CW, CAP, ID)                                                                              \
-  if (cin == 64 && variant == REGW_BASE + BEVAMD_CODE(KC, MT, RW, CW, ID)) return run_r<DT, KC, 64, 4, MT, RW, CW, CAP, ((ID) & ~3)>(sa, stream); \
-  if constexpr (((ID) & ~3) == 0 && RW * 16 * MT != BAKED_ROWS) if (cin == 64 && variant == PERSIST_BASE + BEVAMD_CODE(KC, MT, RW, CW, ID)) return run_p<DT, KC, 64, 4, MT, RW, CW, CAP>(sa, stream);
-#define BEVAMD_CASE128(KC, MT, RW, CW, CAP, ID)                                                                               \
-  if (cin == 128 && variant == REGW_BASE + BEVAMD_CODE(KC, MT, RW, CW, ID)) return run_r<DT, KC, 128, 8, MT, RW, CW, CAP, ((ID) & ~3)>(sa, stream); \
-  if constexpr (((ID) & ~3) == 0 && RW * 16 * MT != BAKED_ROWS) if (cin == 128 && variant == PERSIST_BASE + BEVAMD_CODE(KC, MT, RW, CW, ID)) return run_p<DT, KC, 128, 8, MT, RW, CW, CAP>(sa, stream);
-  BEVAMD_SLABR_SHAPES_32(BEVAMD_CASE32)
-  BEVAMD_SLABR_SHAPES_64(BEVAMD_CASE64)
-  BEVAMD_SLABR_SHAPES_128(BEVAMD_CASE128)
-#undef BEVAMD_CASE32
-#undef BEVAMD_CASE64
-#undef BEVAMD_CASE128
-#undef BEVAMD_CODE
+#define BEVAMD_CASE(C, KC, MT, RW, CW, CAP, ID)                                                                                  \
+  if (cin == C && variant == variant_code(ShapeR{KC, MT, RW, CW, CAP, ID})) return run_r<DT, KC, C, C / 16, MT, RW, CW, CAP, ((ID) & ~3)>(sa, stream); \
+  if constexpr (has_persistent_twin(ShapeR{KC, MT, RW, CW, CAP, ID}))                                                               \
+    if (cin == C && variant == variant_code(ShapeR{KC, MT, RW, CW, CAP, ID}) + (PERSIST_BASE - REGW_BASE)) return run_p<DT, KC, C, C / 16, MT, RW, CW, CAP>(sa, stream);
+  BEVAMD_SLABR_SHAPES_32(BEVAMD_WIDTH32)
+  BEVAMD_SLABR_SHAPES_64(BEVAMD_WIDTH64)
+  BEVAMD_SLABR_SHAPES_128(BEVAMD_WIDTH128)
+#undef BEVAMD_CASE
   set_error("spconv slab: variant %d is listed but not built for cin=%d", variant, cin);
   return BEVAMD_ERR_UNSUPPORTED;
 }
@@ -352,21 +322,18 @@ int launch_impl(const SlabArgs& sa, int cin, int nt, int variant, hipStream_t st
     return BEVAMD_ERR_UNSUPPORTED;
   }
   const int code = variant_code(*s);
-#define BEVAMD_CASE32(KC, MT, NW, SPS, WR, CAP) \
-  if (cin == 32 && code == KC * 10000 + MT * 1000 + (NW / 4) * 100 + SPS * 10 + WR) return run<DT, KC, 32, 2, MT, NW, SPS, WR, CAP>(sa, stream);
-#define BEVAMD_CASE64(KC, MT, NW, SPS, WR, CAP) \
-  if (cin == 64 && code == KC * 10000 + MT * 1000 + (NW / 4) * 100 + SPS * 10 + WR) return run<DT, KC, 64, 4, MT, NW, SPS, WR, CAP>(sa, stream);
-#define BEVAMD_CASE128(KC, MT, NW, SPS, WR, CAP) \
-  if (cin == 128 && code == KC * 10000 + MT * 1000 + (NW / 4) * 100 + SPS * 10 + WR) return run<DT, KC, 128, 8, MT, NW, SPS, WR, CAP>(sa, stream);
-  BEVAMD_SLAB_SHAPES_32(BEVAMD_CASE32)
-  BEVAMD_SLAB_SHAPES_64(BEVAMD_CASE64)
-  BEVAMD_SLAB_SHAPES_128(BEVAMD_CASE128)
-#undef BEVAMD_CASE32
-#undef BEVAMD_CASE64
-#undef BEVAMD_CASE128
+#define BEVAMD_CASE(C, KC, MT, NW, SPS, WR, CAP) \
+  if (cin == C && code == variant_code(Shape{KC, MT, NW, SPS, WR, CAP})) return run<DT, KC, C, C / 16, MT, NW, SPS, WR, CAP>(sa, stream);
+  BEVAMD_SLAB_SHAPES_32(BEVAMD_WIDTH32)
+  BEVAMD_SLAB_SHAPES_64(BEVAMD_WIDTH64)
+  BEVAMD_SLAB_SHAPES_128(BEVAMD_WIDTH128)
+#undef BEVAMD_CASE
   set_error("spconv slab: variant %d is listed but not built for cin=%d", code, cin);
   return BEVAMD_ERR_UNSUPPORTED;
 }
+#undef BEVAMD_WIDTH32
+#undef BEVAMD_WIDTH64
+#undef BEVAMD_WIDTH128
 
 }  // namespace slab
 }  // namespace bevamd

@@ -655,6 +655,55 @@ static inline int image_chunks(int K, int cinp) {  // padded chunk count
 }
 static inline size_t image_elems(int K, int cinp, int nt) { return (size_t)image_chunks(K, cinp) * nt * 64 * 8; }
 
+// ---- the argument contract of the fused 16-bit forward entry points (bevamd_spconv_conv_forward_tiled, _tiled_slots, _slab) ----
+// "features x filter image -> epilogue(bias, folded BatchNorm, residual, ReLU)": what the three share.  They differ in how the
+// rulebook arrives and in what their kernels can address.
+struct ConvIO {
+  const void* features; int dtype, feat_stride, num_in;
+  const void* image;
+  void* out; int out_stride;
+  const void* bias; const float* scale; const float* shift;
+  const void* residual; int residual_stride, relu;
+  int num_out; const int* num_out_dev;
+  int cin, cout, cinp;   // cinp: the padded input width the kernels read (0 = none; the entry point reports that after the buffers)
+};
+struct FeatureLimit { unsigned long long bytes; const char* pitch_note; const char* text; };
+// the gather kernels mark a missing neighbour with the byte offset OOB = 2^31, which must lie past the end of the feature buffer
+constexpr FeatureLimit GATHER_LIMIT = {0x80000000ull, " (zero-padded)", "feature matrix must be < 2 GiB"};
+enum ConvStage { AFTER_DTYPE, AFTER_SIZES, AFTER_BUFFERS, AFTER_LIMIT };   // where an entry point's own checks run
+
+// Validates `io` in the order the entry points document and fills `a` (rulebook fields empty, K = 27: the caller sets its own).
+// own(stage) runs the entry point's own checks between the shared ones and returns their code; `rulebook`: its own buffers are there.
+// Returns BEVAMD_OK without filling `a` when num_out == 0: nothing to launch.
+template <class Own>
+static inline int conv_args(const char* name, const ConvIO& io, bool rulebook, const FeatureLimit& limit, Own own, Args& a) {
+  BEVAMD_REQUIRE(io.dtype == T_F16 || io.dtype == T_BF16, "%s: dtype %d is not 16-bit", name, io.dtype);
+  if (const int rc = own(AFTER_DTYPE)) return rc;
+  BEVAMD_REQUIRE(io.cin > 0 && io.cout > 0 && io.num_out >= 0 && io.num_in >= 0, "%s: bad sizes", name);
+  if (const int rc = own(AFTER_SIZES)) return rc;
+  if (io.num_out == 0) return BEVAMD_OK;
+  BEVAMD_REQUIRE(io.features && io.image && rulebook && io.out, "%s: null buffer", name);
+  if (const int rc = own(AFTER_BUFFERS)) return rc;
+  // rows are read with 16-byte buffer loads of cinp channels: the row pitch must cover them
+  BEVAMD_REQUIRE(io.feat_stride >= io.cinp && io.feat_stride % 8 == 0 && ((uintptr_t)io.features & 15) == 0,
+                 "%s: feature pitch %d must be a multiple of 8 and >= %d%s, 16-byte aligned", name, io.feat_stride, io.cinp, limit.pitch_note);
+  BEVAMD_REQUIRE((unsigned long long)io.num_in * (unsigned long long)io.feat_stride * 2ull < limit.bytes, "%s: %s", name, limit.text);
+  if (const int rc = own(AFTER_LIMIT)) return rc;
+  BEVAMD_REQUIRE(io.out_stride >= io.cout && (!io.residual || io.residual_stride >= io.cout), "%s: bad output pitch", name);
+  BEVAMD_REQUIRE((io.scale == nullptr) == (io.shift == nullptr), "%s: scale and shift go together", name);
+  a.feat = io.features; a.wimg = io.image; a.m_dev = io.num_out_dev; a.out = io.out;
+  a.bias = io.bias; a.scale = io.scale; a.shift = io.shift; a.residual = io.residual;
+  a.feat_stride = io.feat_stride; a.n_in = io.num_in; a.m_cap = io.num_out;
+  a.cout = io.cout; a.out_stride = io.out_stride; a.res_stride = io.residual_stride; a.relu = io.relu;
+  // 16-byte row-wise epilogue: 8-channel groups must be whole and 16-byte aligned everywhere they are touched
+  a.row_epilogue = io.cout % 8 == 0 && io.out_stride % 8 == 0 && ((uintptr_t)io.out & 15) == 0 &&
+                   (!io.residual || (io.residual_stride % 8 == 0 && ((uintptr_t)io.residual & 15) == 0)) &&
+                   (!io.bias || ((uintptr_t)io.bias & 15) == 0) && (!io.scale || (((uintptr_t)io.scale | (uintptr_t)io.shift) & 15) == 0);
+  a.nbr = nullptr; a.nbr_stride = 0; a.K = 27;
+  a.hdr = nullptr; a.slots = nullptr; a.slab_rows = 0;
+  return BEVAMD_OK;
+}
+
 // implemented once per dtype (spconv_tile_f16.hip / spconv_tile_bf16.hip)
 int launch_f16(const Args& a, int cinp, int nt, int variant, hipStream_t stream);
 int launch_bf16(const Args& a, int cinp, int nt, int variant, hipStream_t stream);

@@ -132,31 +132,21 @@ int bevamd_spconv_conv_forward_tiled(const void* features, int dtype, int feat_s
                                      const float* bn_scale, const float* bn_shift, const void* residual,
                                      int residual_stride, int relu, int variant, void* stream_) {
   hipStream_t stream = (hipStream_t)stream_;
-  BEVAMD_REQUIRE(dtype == tile::T_F16 || dtype == tile::T_BF16, "spconv_conv_forward_tiled: dtype %d is not 16-bit", dtype);
-  BEVAMD_REQUIRE(kernel_volume > 0 && cin > 0 && cout > 0 && num_out >= 0 && num_in >= 0, "spconv_conv_forward_tiled: bad sizes");
-  if (num_out == 0) return BEVAMD_OK;
-  BEVAMD_REQUIRE(features && image && nbr && out, "spconv_conv_forward_tiled: null buffer");
-  BEVAMD_REQUIRE(nbr_stride >= num_out, "spconv_conv_forward_tiled: nbr_stride %d < num_out %d", nbr_stride, num_out);
+  static const char* const name = "spconv_conv_forward_tiled";
   const int cinp = tile::pad_cin(cin), nt = tile::pad_nt(cout);
-  BEVAMD_REQUIRE(cinp && nt, "spconv_conv_forward_tiled: channels %d -> %d exceed 128", cin, cout);
-  // rows are read with 16-byte buffer loads of cin_pad channels: the row pitch must cover them
-  BEVAMD_REQUIRE(feat_stride >= cinp && feat_stride % 8 == 0 && ((uintptr_t)features & 15) == 0,
-                 "spconv_conv_forward_tiled: feature pitch %d must be a multiple of 8 and >= %d (zero-padded), 16-byte aligned",
-                 feat_stride, cinp);
-  BEVAMD_REQUIRE((unsigned long long)num_in * feat_stride * 2ull < 0x80000000ull,
-                 "spconv_conv_forward_tiled: feature matrix must be < 2 GiB");
-  BEVAMD_REQUIRE(out_stride >= cout && (!residual || residual_stride >= cout), "spconv_conv_forward_tiled: bad output pitch");
-  BEVAMD_REQUIRE((bn_scale == nullptr) == (bn_shift == nullptr), "spconv_conv_forward_tiled: scale and shift go together");
+  const tile::ConvIO io = {features, dtype, feat_stride, num_in, image, out, out_stride, bias, bn_scale, bn_shift,
+                           residual, residual_stride, relu, num_out, num_out_dev, cin, cout, cinp};
   tile::Args a;
-  a.hdr = nullptr; a.slots = nullptr; a.slab_rows = 0;
-  a.feat = features; a.wimg = image; a.nbr = nbr; a.m_dev = num_out_dev; a.out = out;
-  a.bias = bias; a.scale = bn_scale; a.shift = bn_shift; a.residual = residual;
-  a.feat_stride = feat_stride; a.n_in = num_in; a.nbr_stride = nbr_stride; a.m_cap = num_out; a.K = kernel_volume;
-  a.cout = cout; a.out_stride = out_stride; a.res_stride = residual_stride; a.relu = relu;
-  // 16-byte row-wise epilogue: 8-channel groups must be whole and 16-byte aligned everywhere they are touched
-  a.row_epilogue = cout % 8 == 0 && out_stride % 8 == 0 && ((uintptr_t)out & 15) == 0 &&
-                   (!residual || (residual_stride % 8 == 0 && ((uintptr_t)residual & 15) == 0)) &&
-                   (!bias || ((uintptr_t)bias & 15) == 0) && (!bn_scale || (((uintptr_t)bn_scale | (uintptr_t)bn_shift) & 15) == 0);
+  const int rc = tile::conv_args(name, io, nbr != nullptr, tile::GATHER_LIMIT, [&](tile::ConvStage at) {
+    if (at == tile::AFTER_DTYPE) BEVAMD_REQUIRE(kernel_volume > 0, "%s: bad sizes", name);
+    if (at == tile::AFTER_BUFFERS) {
+      BEVAMD_REQUIRE(nbr_stride >= num_out, "%s: nbr_stride %d < num_out %d", name, nbr_stride, num_out);
+      BEVAMD_REQUIRE(cinp && nt, "%s: channels %d -> %d exceed 128", name, cin, cout);
+    }
+    return BEVAMD_OK;
+  }, a);
+  if (rc != BEVAMD_OK || num_out == 0) return rc;
+  a.nbr = nbr; a.nbr_stride = nbr_stride; a.K = kernel_volume;
   return dtype == tile::T_F16 ? tile::launch_f16(a, cinp, nt, variant, stream) : tile::launch_bf16(a, cinp, nt, variant, stream);
 }
 
@@ -171,29 +161,18 @@ int bevamd_spconv_conv_forward_tiled_slots(const void* features, int dtype, int 
                                            const void* bias, const float* bn_scale, const float* bn_shift, const void* residual,
                                            int residual_stride, int relu, int variant, void* stream_) {
   hipStream_t stream = (hipStream_t)stream_;
-  BEVAMD_REQUIRE(dtype == tile::T_F16 || dtype == tile::T_BF16, "spconv_conv_forward_tiled_slots: dtype %d is not 16-bit", dtype);
-  BEVAMD_REQUIRE(cin > 0 && cout > 0 && num_out >= 0 && num_in >= 0, "spconv_conv_forward_tiled_slots: bad sizes");
-  BEVAMD_REQUIRE(block_rows == 128 || block_rows == 256, "spconv_conv_forward_tiled_slots: block_rows %d (128 | 256)", block_rows);
-  if (num_out == 0) return BEVAMD_OK;
-  BEVAMD_REQUIRE(features && image && hdr && slots && out, "spconv_conv_forward_tiled_slots: null buffer");
+  static const char* const name = "spconv_conv_forward_tiled_slots";
   const int cinp = tile::pad_cin(cin), nt = tile::pad_nt(cout);
-  BEVAMD_REQUIRE(cinp && nt, "spconv_conv_forward_tiled_slots: channels %d -> %d exceed 128", cin, cout);
-  BEVAMD_REQUIRE(feat_stride >= cinp && feat_stride % 8 == 0 && ((uintptr_t)features & 15) == 0,
-                 "spconv_conv_forward_tiled_slots: feature pitch %d must be a multiple of 8 and >= %d (zero-padded), 16-byte aligned",
-                 feat_stride, cinp);
-  BEVAMD_REQUIRE((unsigned long long)num_in * feat_stride * 2ull < 0x80000000ull,
-                 "spconv_conv_forward_tiled_slots: feature matrix must be < 2 GiB");
-  BEVAMD_REQUIRE(out_stride >= cout && (!residual || residual_stride >= cout), "spconv_conv_forward_tiled_slots: bad output pitch");
-  BEVAMD_REQUIRE((bn_scale == nullptr) == (bn_shift == nullptr), "spconv_conv_forward_tiled_slots: scale and shift go together");
+  const tile::ConvIO io = {features, dtype, feat_stride, num_in, image, out, out_stride, bias, bn_scale, bn_shift,
+                           residual, residual_stride, relu, num_out, num_out_dev, cin, cout, cinp};
   tile::Args a;
+  const int rc = tile::conv_args(name, io, hdr && slots, tile::GATHER_LIMIT, [&](tile::ConvStage at) {
+    if (at == tile::AFTER_SIZES) BEVAMD_REQUIRE(block_rows == 128 || block_rows == 256, "%s: block_rows %d (128 | 256)", name, block_rows);
+    if (at == tile::AFTER_BUFFERS) BEVAMD_REQUIRE(cinp && nt, "%s: channels %d -> %d exceed 128", name, cin, cout);
+    return BEVAMD_OK;
+  }, a);
+  if (rc != BEVAMD_OK || num_out == 0) return rc;
   a.hdr = (const int2*)hdr; a.slots = (const uint16_t*)slots; a.slab_rows = block_rows;
-  a.feat = features; a.wimg = image; a.nbr = nullptr; a.m_dev = num_out_dev; a.out = out;
-  a.bias = bias; a.scale = bn_scale; a.shift = bn_shift; a.residual = residual;
-  a.feat_stride = feat_stride; a.n_in = num_in; a.nbr_stride = 0; a.m_cap = num_out; a.K = 27;
-  a.cout = cout; a.out_stride = out_stride; a.res_stride = residual_stride; a.relu = relu;
-  a.row_epilogue = cout % 8 == 0 && out_stride % 8 == 0 && ((uintptr_t)out & 15) == 0 &&
-                   (!residual || (residual_stride % 8 == 0 && ((uintptr_t)residual & 15) == 0)) &&
-                   (!bias || ((uintptr_t)bias & 15) == 0) && (!bn_scale || (((uintptr_t)bn_scale | (uintptr_t)bn_shift) & 15) == 0);
   return dtype == tile::T_F16 ? tile::launch_f16(a, cinp, nt, variant, stream) : tile::launch_bf16(a, cinp, nt, variant, stream);
 }
 

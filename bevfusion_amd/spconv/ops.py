@@ -341,6 +341,32 @@ def make_filter_images(specs, dtype, device):
     return out
 
 
+def _conv_forward(entry, features, image, rulebook, num_out, sizes, cin, cout, bias, bn_scale, bn_shift, residual, relu, num_out_dev,
+                  out, variant):
+    """What the three fused 16-bit forward wrappers share (C side: tile::conv_args).  `entry`: the C function without its
+    prefix; rulebook(): its rulebook arguments (between `image` and num_out; not evaluated when there are no rows); `sizes`: what
+    it takes between num_out_dev and cin."""
+    lib = _capi.load()
+    _require_cuda(features, "features")
+    if features.stride(1) != 1:
+        features = features.contiguous()
+    dt = _dtype_code(features)
+    if out is None:
+        out = torch.empty((num_out, cout), dtype=features.dtype, device=features.device)
+    if num_out == 0:
+        return out
+    if residual is not None and residual.stride(1) != 1:
+        residual = residual.contiguous()
+    with torch.cuda.device(features.device):
+        rc = getattr(lib, "bevamd_" + entry)(
+            _capi.ptr(features), dt, features.stride(0), features.shape[0], _capi.ptr(image), *rulebook(), int(num_out),
+            _capi.ptr(num_out_dev), *sizes, int(cin), int(cout), _capi.ptr(out), out.stride(0), _capi.ptr(bias), _capi.ptr(bn_scale),
+            _capi.ptr(bn_shift), _capi.ptr(residual), residual.stride(0) if residual is not None else 0, int(bool(relu)),
+            int(variant), _capi.stream_ptr(features.device))
+    _capi.check(rc, entry)
+    return out
+
+
 def sparse_conv_tiled(features, image, nbr, num_out, kernel_volume, cin, cout, bias=None, bn_scale=None, bn_shift=None,
                       residual=None, relu=False, num_out_dev=None, out=None, variant=0):
     """One fused launch: out[o] = relu?(bn_scale * (sum_k features[nbr[k, o]] @ W[k] + bias) + bn_shift + residual[o]).
@@ -348,51 +374,15 @@ def sparse_conv_tiled(features, image, nbr, num_out, kernel_volume, cin, cout, b
     features [num_in, pitch >= padded_channels(cin)] 16-bit with zero padding channels; `image` from
     `make_filter_image`; `num_out` bounds the launch, `num_out_dev` (int32 device scalar, optional) is the live row
     count so that no host sync is needed.  Rows >= the live count of `out` are left untouched."""
-    lib = _capi.load()
-    _require_cuda(features, "features")
-    if features.stride(1) != 1:
-        features = features.contiguous()
-    dt = _dtype_code(features)
-    if out is None:
-        out = torch.empty((num_out, cout), dtype=features.dtype, device=features.device)
-    if num_out == 0:
-        return out
-    if residual is not None and residual.stride(1) != 1:
-        residual = residual.contiguous()
-    with torch.cuda.device(features.device):
-        rc = lib.bevamd_spconv_conv_forward_tiled(
-            _capi.ptr(features), dt, features.stride(0), features.shape[0], _capi.ptr(image), _capi.ptr(nbr),
-            nbr.stride(0), int(num_out), _capi.ptr(num_out_dev), int(kernel_volume), int(cin), int(cout), _capi.ptr(out),
-            out.stride(0), _capi.ptr(bias), _capi.ptr(bn_scale), _capi.ptr(bn_shift), _capi.ptr(residual),
-            residual.stride(0) if residual is not None else 0, int(bool(relu)), int(variant),
-            _capi.stream_ptr(features.device))
-    _capi.check(rc, "spconv_conv_forward_tiled")
-    return out
+    return _conv_forward("spconv_conv_forward_tiled", features, image, lambda: (_capi.ptr(nbr), nbr.stride(0)), num_out,
+                         (int(kernel_volume),), cin, cout, bias, bn_scale, bn_shift, residual, relu, num_out_dev, out, variant)
 
 
 def sparse_conv_tiled_slots(features, image, meta, num_out, cin, cout, bias=None, bn_scale=None, bn_shift=None, residual=None,
                             relu=False, num_out_dev=None, out=None, variant=0):
     """`sparse_conv_tiled` for a 3x3x3 convolution whose rulebook is slab metadata (`SlabMeta`) instead of the int32 table."""
-    lib = _capi.load()
-    _require_cuda(features, "features")
-    if features.stride(1) != 1:
-        features = features.contiguous()
-    dt = _dtype_code(features)
-    if out is None:
-        out = torch.empty((num_out, cout), dtype=features.dtype, device=features.device)
-    if num_out == 0:
-        return out
-    if residual is not None and residual.stride(1) != 1:
-        residual = residual.contiguous()
-    with torch.cuda.device(features.device):
-        rc = lib.bevamd_spconv_conv_forward_tiled_slots(
-            _capi.ptr(features), dt, features.stride(0), features.shape[0], _capi.ptr(image), _capi.ptr(meta.hdr),
-            _capi.ptr(meta.slots), meta.block_rows, int(num_out), _capi.ptr(num_out_dev), int(cin), int(cout), _capi.ptr(out),
-            out.stride(0), _capi.ptr(bias), _capi.ptr(bn_scale), _capi.ptr(bn_shift), _capi.ptr(residual),
-            residual.stride(0) if residual is not None else 0, int(bool(relu)), int(variant),
-            _capi.stream_ptr(features.device))
-    _capi.check(rc, "spconv_conv_forward_tiled_slots")
-    return out
+    return _conv_forward("spconv_conv_forward_tiled_slots", features, image, lambda: (_capi.ptr(meta.hdr), _capi.ptr(meta.slots), meta.block_rows),
+                         num_out, (), cin, cout, bias, bn_scale, bn_shift, residual, relu, num_out_dev, out, variant)
 
 
 # ---- slab (staged-rows) SubM convolution: csrc/spconv_slab.h ------------------------------------------------------------
@@ -421,15 +411,25 @@ class SlabMeta:
         self.hdr, self.slots, self.block_rows, self.status = hdr, slots, block_rows, status
 
 
+def _status_or_zero(status, dev):
+    if status is None:   # callers on a hot path hand in a slice of one pre-zeroed pool (a 5 us fill kernel per product otherwise)
+        status = torch.zeros(1, dtype=torch.int32, device=dev)
+    return status
+
+
+def _slab_buffers(lib, m_cap, block_rows, status, dev):
+    """(hdr, slots, status) of the metadata of m_cap rows in blocks of block_rows (call under the device guard)."""
+    hdr = torch.empty(max(lib.bevamd_spconv_slab_hdr_bytes(int(m_cap), int(block_rows)), 16), dtype=torch.uint8, device=dev)
+    slots = torch.empty(max(lib.bevamd_spconv_slab_slot_bytes(int(m_cap), int(block_rows)), 16), dtype=torch.uint8, device=dev)
+    return hdr, slots, _status_or_zero(status, dev)
+
+
 def slab_build(nbr, m_cap, m_dev, block_rows, stream_ptr=None, status=None):
     lib = _capi.load()
     dev = nbr.device
     assert nbr.shape[0] == 27 and nbr.dtype == torch.int32
     with torch.cuda.device(dev):
-        hdr = torch.empty(max(lib.bevamd_spconv_slab_hdr_bytes(int(m_cap), int(block_rows)), 16), dtype=torch.uint8, device=dev)
-        slots = torch.empty(max(lib.bevamd_spconv_slab_slot_bytes(int(m_cap), int(block_rows)), 16), dtype=torch.uint8, device=dev)
-        if status is None:   # callers on a hot path hand in a slice of one pre-zeroed pool (a 5 us fill kernel per product otherwise)
-            status = torch.zeros(1, dtype=torch.int32, device=dev)
+        hdr, slots, status = _slab_buffers(lib, m_cap, block_rows, status, dev)
         rc = lib.bevamd_spconv_slab_build(_capi.ptr(nbr), nbr.stride(0), int(m_cap), _capi.ptr(m_dev), int(block_rows),
                                           _capi.ptr(hdr), _capi.ptr(slots), _capi.ptr(status),
                                           stream_ptr if stream_ptr is not None else _capi.stream_ptr(dev))
@@ -442,10 +442,7 @@ def slab_build_from_index(indices, m_cap, m_dev, batch, shape, index_kind, index
     lib = _capi.load()
     dev = indices.device
     with torch.cuda.device(dev):
-        hdr = torch.empty(max(lib.bevamd_spconv_slab_hdr_bytes(int(m_cap), int(block_rows)), 16), dtype=torch.uint8, device=dev)
-        slots = torch.empty(max(lib.bevamd_spconv_slab_slot_bytes(int(m_cap), int(block_rows)), 16), dtype=torch.uint8, device=dev)
-        if status is None:   # callers on a hot path hand in a slice of one pre-zeroed pool (a 5 us fill kernel per product otherwise)
-            status = torch.zeros(1, dtype=torch.int32, device=dev)
+        hdr, slots, status = _slab_buffers(lib, m_cap, block_rows, status, dev)
         rc = lib.bevamd_spconv_slab_build_from_index(_capi.ptr(indices), int(m_cap), _capi.ptr(m_dev), int(batch),
                                                      _capi.ints(shape), int(index_kind), _capi.ptr(index), int(index_n_cap),
                                                      int(block_rows), _capi.ptr(hdr), _capi.ptr(slots), _capi.ptr(status),
@@ -462,8 +459,7 @@ def sorted_index_build(indices, n_cap, n_dev, batch, shape, stream_ptr=None, sta
     with torch.cuda.device(dev):
         nbytes = int(lib.bevamd_spconv_sorted_index_bytes(int(n_cap), int(batch), _capi.ints(shape)))
         index = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dev)
-        if status is None:   # callers on a hot path hand in a slice of one pre-zeroed pool (a 5 us fill kernel per product otherwise)
-            status = torch.zeros(1, dtype=torch.int32, device=dev)
+        status = _status_or_zero(status, dev)
         rc = lib.bevamd_spconv_sorted_index_build(_capi.ptr(indices), int(n_cap), _capi.ptr(n_dev), int(batch), _capi.ints(shape),
                                                   _capi.ptr(index), nbytes, _capi.ptr(status),
                                                   stream_ptr if stream_ptr is not None else _capi.stream_ptr(dev))
@@ -478,10 +474,7 @@ def slab_build_from_sorted(out_indices, m_cap, m_dev, batch, in_shape, out_shape
     lib = _capi.load()
     dev = out_indices.device
     with torch.cuda.device(dev):
-        hdr = torch.empty(max(lib.bevamd_spconv_slab_hdr_bytes(int(m_cap), int(block_rows)), 16), dtype=torch.uint8, device=dev)
-        slots = torch.empty(max(lib.bevamd_spconv_slab_slot_bytes(int(m_cap), int(block_rows)), 16), dtype=torch.uint8, device=dev)
-        if status is None:   # callers on a hot path hand in a slice of one pre-zeroed pool (a 5 us fill kernel per product otherwise)
-            status = torch.zeros(1, dtype=torch.int32, device=dev)
+        hdr, slots, status = _slab_buffers(lib, m_cap, block_rows, status, dev)
         rc = lib.bevamd_spconv_slab_build_from_sorted(_capi.ptr(out_indices), int(m_cap), _capi.ptr(m_dev), int(batch),
                                                       _capi.ints(in_shape), _capi.ints(out_shape), _capi.ints(stride),
                                                       _capi.ints(padding), int(bool(subm)), _capi.ptr(in_index), int(in_n_cap),
@@ -495,26 +488,8 @@ def sparse_conv_slab(features, image, meta, num_out, cin, cout, bias=None, bn_sc
                      relu=False, num_out_dev=None, out=None, variant=0):
     """`sparse_conv_tiled` for a 3x3x3 convolution over linear-index-ordered rows, through the slab kernels (SubM with
     cin == cout in {32, 64, 128}; cin <= 16 with cout in {16, 32}: SubM or strided, depending on what `meta` describes)."""
-    lib = _capi.load()
-    _require_cuda(features, "features")
-    if features.stride(1) != 1:
-        features = features.contiguous()
-    dt = _dtype_code(features)
-    if out is None:
-        out = torch.empty((num_out, cout), dtype=features.dtype, device=features.device)
-    if num_out == 0:
-        return out
-    if residual is not None and residual.stride(1) != 1:
-        residual = residual.contiguous()
-    with torch.cuda.device(features.device):
-        rc = lib.bevamd_spconv_conv_forward_slab(
-            _capi.ptr(features), dt, features.stride(0), features.shape[0], _capi.ptr(image), _capi.ptr(meta.hdr),
-            _capi.ptr(meta.slots), meta.block_rows, int(num_out), _capi.ptr(num_out_dev), int(cin), int(cout), _capi.ptr(out),
-            out.stride(0), _capi.ptr(bias), _capi.ptr(bn_scale), _capi.ptr(bn_shift), _capi.ptr(residual),
-            residual.stride(0) if residual is not None else 0, int(bool(relu)), int(variant),
-            _capi.stream_ptr(features.device))
-    _capi.check(rc, "spconv_conv_forward_slab")
-    return out
+    return _conv_forward("spconv_conv_forward_slab", features, image, lambda: (_capi.ptr(meta.hdr), _capi.ptr(meta.slots), meta.block_rows),
+                         num_out, (), cin, cout, bias, bn_scale, bn_shift, residual, relu, num_out_dev, out, variant)
 
 
 def _pad_channels(features, pitch):
