@@ -162,6 +162,12 @@ _EXT_SIGNATURES = {
     "bevamd_pillar_stack_forward": (I, [P, P, P, I, I, I, I, I, P, I, P, P, P, P, P, P]),
     "bevamd_pillar_scatter_forward": (I, [P, I, P, I, I, I, I, I, P, P, P]),
     "bevamd_pillar_scatter_backward": (I, [P, I, P, P, I, I, I, I, I, P, P]),
+    # TransFusion head ends
+    "bevamd_head_proposals_workspace_bytes": (Z, [I, I, I, I]),
+    "bevamd_head_proposals": (I, [P, I, I, I, I, I, ctypes.c_ulonglong, I, P, P, P, P, Z, P]),
+    "bevamd_head_gather_queries": (I, [P, I, I, I, I, I, ctypes.c_ulonglong, P, I, P, I, I, P, I, P, P, P, P]),
+    "bevamd_transfusion_decode": (I, [P, P, P, P, P, P, P, P, I, I, I, I, P, P, c_float, I, P, P, P, P, P]),
+    "bevamd_circle_nms": (I, [P, P, I, P, I, P, I, I, P, P, P, P, P]),
 }
 
 

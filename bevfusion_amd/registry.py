@@ -58,6 +58,7 @@ CONV_LAYERS = Registry("conv layer")
 NORM_LAYERS = Registry("norm layer")
 BACKBONES = Registry("backbone")
 VTRANSFORMS = Registry("vtransform")
+BBOX_CODERS = Registry("bbox coder")
 
 for _name, _cls in (("BN", nn.BatchNorm2d), ("BN1d", nn.BatchNorm1d), ("BN2d", nn.BatchNorm2d),
                     ("BN3d", nn.BatchNorm3d), ("SyncBN", nn.SyncBatchNorm), ("GN", nn.GroupNorm), ("LN", nn.LayerNorm)):
@@ -98,13 +99,15 @@ def build_norm_layer(cfg, num_features, postfix=""):
 
 def register_everywhere(registry_name, cls, name=None):
     """Register in our registry and, if mmcv/mmdet/mmdet3d are importable, in theirs too."""
-    ours = {"conv": CONV_LAYERS, "backbone": BACKBONES, "vtransform": VTRANSFORMS}[registry_name]
+    ours = {"conv": CONV_LAYERS, "backbone": BACKBONES, "vtransform": VTRANSFORMS, "bbox_coder": BBOX_CODERS}[registry_name]
     ours.register_module(name=name, module=cls, force=True)
     try:  # pragma: no cover - mmcv is not installed in this image
         if registry_name == "conv":
             from mmcv.cnn import CONV_LAYERS as REAL
         elif registry_name == "backbone":
             from mmdet.models import BACKBONES as REAL
+        elif registry_name == "bbox_coder":
+            from mmdet.core.bbox.builder import BBOX_CODERS as REAL
         else:
             from mmdet3d.models.builder import VTRANSFORMS as REAL
         REAL.register_module(name=name, module=cls, force=True)

@@ -98,6 +98,65 @@ int bevamd_pillar_scatter_backward(const void* grad_canvas, int dtype, const int
                                    int num_pillars, int channels, int batch_size, int nx, int ny, void* grad_feats,
                                    void* stream);
 
+
+/* The two non-learned ends of TransFusionHead.  Nothing below synchronises the device or reads anything back; every call is a
+ * fixed, small number of launches on `stream` and can be captured in a graph.  All heatmap inputs must be FINITE.
+ *
+ * bevamd_head_proposals: replaces mmdet3d/models/heads/bbox/transfusion.py:239-274 (sigmoid, max_pool2d into a zero-padded
+ *   local_max, the two class overwrites, compare, multiply, full argsort).  logits [batch, classes, height, width] fp32, FINITE.
+ *   s = sigmoid(x); for a class whose bit is clear in exempt_mask, s is kept only where it equals the maximum of its
+ *   kernel_size x kernel_size window (odd, <= height and width) and is 0 closer than kernel_size / 2 to the border; classes
+ *   >= 64 are never exempt.  The proposals are the num_proposals (1 .. 1024, <= classes * height * width) largest of the
+ *   classes * height * width values of a sample in STABLE descending order: equal values — ties, and the zeros that fill the
+ *   list when fewer cells survive — come in ascending flat index c * height * width + y * width + x (the reference's argsort
+ *   leaves that order open).  top_class, top_index (position in height * width) [batch, num_proposals] int64, top_score fp32.
+ *   No sort of the map: candidates are compacted, an MSB radix select finds the K-th key, one workgroup per sample sorts K keys.
+ *   ws: bevamd_head_proposals_workspace_bytes (0 for sizes the call rejects); it needs no initialisation.
+ * bevamd_head_gather_queries: replaces transfusion.py:275-295 and :322-325.  query_feat [batch, feat_channels, num_proposals]
+ *   from feat [batch, feat_channels, height * width] (feat_dtype 0 fp32, 1 fp16); query_pos [batch, num_proposals, 2] from
+ *   bev_pos [bev_pos_batch = 1 or batch, height * width, 2]; query_heatmap_score [batch, classes, num_proposals]: the suppressed
+ *   sigmoid of EVERY class at each proposal's position, recomputed from the logits by the function bevamd_head_proposals uses
+ *   (same bits as top_score).  A top_index outside [0, height * width) reads nothing and yields zeros.
+ * bevamd_transfusion_decode: replaces transfusion.py:725-749 and TransFusionBBoxCoder.decode(filter=True)
+ *   (mmdet3d/core/bbox/coders/transfusion_bbox_coder.py:39-124).  heatmap [batch, classes, pitch] logits, center [batch, 2, pitch],
+ *   height [batch, 1, pitch], dim [batch, 3, pitch], rot [batch, 2, pitch], vel [batch, 2, pitch] or NULL: the LAST num_proposals
+ *   of the pitch columns are decoded; query_heatmap_score [batch, classes, num_proposals], query_labels [batch, num_proposals]
+ *   int64.  coder: HOST {out_size_factor, voxel_size[0], voxel_size[1], pc_range[0], pc_range[1]} as fp32;
+ *   post_center_range: HOST 6 floats or NULL (no range test).  boxes [batch, num_proposals, 7 or 9 with vel] =
+ *   (x * osf * vs + pc, y likewise, height - exp(dim2) * 0.5, exp(dim), atan2(rot0, rot1), vel) in the reference's fp32 operation
+ *   order without FMA contraction (centre and velocity columns are bit-equal to the reference's CPU result; exp / atan2 are
+ *   rounded once from double); scores = max over classes of sigmoid(heatmap) * query_heatmap_score * one_hot(query_labels),
+ *   labels the first class attaining it (query_heatmap_score and query_labels both NULL: heatmap already holds the scores, as
+ *   in TransFusionBBoxCoder.decode called on its own, and pitch columns of it are read likewise); valid uint8 = inside post_center_range on the first three columns AND
+ *   (use_score_threshold == 0 OR score > score_threshold) — the reference skips the score test for a falsy threshold, so the
+ *   caller passes use_score_threshold = 0 for 0.0.  The inputs are NOT modified (the reference overwrites center and dim).
+ * bevamd_circle_nms: replaces circle_nms of mmdet3d/core/post_processing/box3d_nms.py:181-219, segmented.  xy [num_rows, 2],
+ *   score [num_rows], seg_offsets [num_segments + 1] int32 (device), seg_thresh [num_segments] fp32 (device), live: optional uint8
+ *   [num_rows] (0 rows take no part).  Per segment: greedy in descending score (equal scores: lower row first); row j is dropped
+ *   when a kept row i has (xi - xj)^2 + (yi - yj)^2 <= thresh in fp32 — the threshold meets the SQUARED distance, as in the
+ *   reference; only the first post_max_size kept rows stay.  A threshold <= 0 keeps every live row of the segment without the
+ *   cap (transfusion.py:823-824).  keep [num_rows] uint8; keep_order (optional) [num_rows] int64: the kept rows of segment s in
+ *   descending score order at seg_offsets[s] ...; seg_counts [num_segments] int32.  max_segment_rows: the caller's bound on a
+ *   segment's length, at most 1024 (more: 4, unsupported, before any GPU work); a segment longer than the bound keeps nothing
+ *   and reports -1.  No workspace. */
+size_t bevamd_head_proposals_workspace_bytes(int batch, int classes, int height, int width);
+int bevamd_head_proposals(const float* logits, int batch, int classes, int height, int width, int kernel_size,
+                          unsigned long long exempt_mask, int num_proposals, long long* top_class, long long* top_index,
+                          float* top_score, void* ws, size_t ws_bytes, void* stream);
+int bevamd_head_gather_queries(const float* logits, int batch, int classes, int height, int width, int kernel_size,
+                               unsigned long long exempt_mask, const long long* top_index, int num_proposals, const void* feat,
+                               int feat_dtype, int feat_channels, const float* bev_pos, int bev_pos_batch, void* query_feat,
+                               float* query_pos, float* query_heatmap_score, void* stream);
+int bevamd_transfusion_decode(const float* heatmap, const float* center, const float* height, const float* dim,
+                              const float* rot, const float* vel, const float* query_heatmap_score,
+                              const long long* query_labels, int batch, int classes, int num_proposals, int pitch,
+                              const float* coder, const float* post_center_range, float score_threshold,
+                              int use_score_threshold, float* boxes, float* scores, long long* labels, unsigned char* valid,
+                              void* stream);
+int bevamd_circle_nms(const float* xy, const float* score, int num_rows, const int* seg_offsets, int num_segments,
+                      const float* seg_thresh, int max_segment_rows, int post_max_size, const unsigned char* live,
+                      unsigned char* keep, long long* keep_order, int* seg_counts, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
