@@ -157,6 +157,55 @@ int bevamd_circle_nms(const float* xy, const float* score, int num_rows, const i
                       const float* seg_thresh, int max_segment_rows, int post_max_size, const unsigned char* live,
                       unsigned char* keep, long long* keep_order, int* seg_counts, void* stream);
 
+
+/* The non-learned end of CenterHead (mmdet3d/models/heads/bbox/centerpoint.py:637-884 get_bboxes / get_task_detections and
+ * CenterPointBBoxCoder.decode, core/bbox/coders/centerpoint_bbox_coders.py:62-225).  Nothing below synchronises the device or
+ * reads anything back; every call is a fixed number of launches on `stream` for ANY number of tasks and samples and can be
+ * captured in a graph.  Tasks travel as HOST tables (at most 16 tasks of at most 8 classes); the segment of every per-row array
+ * is (sample, task): row = (sample * num_tasks + task) * max_num + k.
+ *
+ * bevamd_centerpoint_select: heatmaps: HOST array of num_tasks DEVICE pointers [batch, task_classes[t], height, width] fp32,
+ *   FINITE; apply_sigmoid 1: logits (get_bboxes), 0: scores (the coder's decode).  Per segment the max_num (1 .. 1024, at most
+ *   height * width, where the reference's per-class topk raises) largest scores in STABLE descending order: equal scores in
+ *   ascending flat index c * height * width + cell, which is what the reference's two-level top-K yields wherever its answer is
+ *   defined.  top_flat [batch, num_tasks, max_num] int32 (that flat index), top_score fp32.  Two launches.
+ *   ws: bevamd_centerpoint_select_workspace_bytes(batch, sum of task_classes, height, width); it needs no initialisation.
+ * bevamd_centerpoint_decode: one launch, one thread per row.  maps: HOST array of 5 * num_tasks DEVICE pointers, per task
+ *   {reg [batch, 2, H, W] or NULL, height [batch, 1, H, W], dim [batch, 3, H, W], rot [batch, 2, H, W], vel [batch, 2, H, W] or
+ *   NULL} (reg / vel: for every task or for none), read at the selected cell only.  boxes [rows, 7 or 9 with vel] =
+ *   ((cell / W + reg0) * osf * vs0 + pc0, (cell % W + reg1) * osf * vs1 + pc1 (+ 0.5 each without reg; the FIRST coordinate is
+ *   the row, as in the reference), height (- dim2 * 0.5 with bottom_centre, centerpoint.py:746), dim (exp(dim) with norm_bbox), atan2(rot0, rot1), vel) in the reference's
+ *   fp32 operation order without FMA contraction; exp / atan2 are rounded once from double.  labels int32: class within the task
+ *   + the classes of the tasks before it.  live uint8 = inside post_center_range (HOST 6 floats, inclusive, on x, y and the
+ *   UNSHIFTED height) AND (use_coder_threshold == 0 OR score > coder_threshold) AND, for a task with task_rotate[t] != 0,
+ *   (use_head_threshold == 0 OR score >= head_threshold).  post_ok uint8 = 1, or for a task_rotate task inside
+ *   post_center_limit_range (HOST 6 floats or NULL: no test).  coder: HOST {out_size_factor, voxel_size[0], voxel_size[1],
+ *   pc_range[0], pc_range[1]} as fp32.  A top_flat outside the task's map yields a dead row of zeros.
+ * bevamd_rotate_nms_segments: nms_gpu (ops/iou3d/iou3d_utils.py:23-48 over iou3d_kernel.cu:264-345 and iou3d.cpp:96-133) on
+ *   num_segments segments of rows_per_segment (1 .. 1024; more: 4, unsupported) rows ALREADY in descending score, one workgroup
+ *   each; segment s belongs to task s % num_tasks.  boxes [rows, box_width >= 7] (x, y, z, w, l, h, yaw, ...): the BEV box is the
+ *   LiDAR convention's (x - w / 2, y - l / 2, x + w / 2, y + l / 2, yaw) with w and l multiplied by
+ *   task_scale[task * 8 + labels[row] - task_label_base[task]] (HOST tables; task_scale NULL: 1, labels may then be NULL).  The
+ *   live rows (live NULL: all) are cut to the first pre_max_size; greedy: a row is dropped when an earlier kept row has rotated
+ *   IoU > task_thresh[task], in the arithmetic of bevamd_iou3d_nms; the first post_max_size kept rows stay, then those with
+ *   post_ok == 0 (NULL: none) are dropped.  A task with task_enabled[t] == 0 (NULL: all enabled) keeps nothing.  keep [rows]
+ *   uint8, seg_counts [num_segments] int32.  No workspace, no K x K mask. */
+size_t bevamd_centerpoint_select_workspace_bytes(int batch, int total_classes, int height, int width);
+int bevamd_centerpoint_select(const void* const* heatmaps, const int* task_classes, int num_tasks, int batch, int height,
+                              int width, int max_num, int apply_sigmoid, int* top_flat, float* top_score, void* ws,
+                              size_t ws_bytes, void* stream);
+int bevamd_centerpoint_decode(const void* const* maps, const int* task_classes, const int* task_rotate, int num_tasks, int batch,
+                              int height, int width, int max_num, const int* top_flat, const float* top_score, int norm_bbox,
+                              int bottom_centre, const float* coder, const float* post_center_range, float coder_threshold,
+                              int use_coder_threshold, float head_threshold, int use_head_threshold,
+                              const float* post_center_limit_range, float* boxes, int* labels, unsigned char* live,
+                              unsigned char* post_ok, void* stream);
+int bevamd_rotate_nms_segments(const float* boxes, int box_width, const int* labels, const unsigned char* live,
+                               const unsigned char* post_ok, int num_segments, int rows_per_segment, int num_tasks,
+                               const int* task_enabled, const float* task_thresh, const int* task_label_base,
+                               const float* task_scale, int pre_max_size, int post_max_size, unsigned char* keep,
+                               int* seg_counts, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
