@@ -17,7 +17,9 @@ inference runs on:
     row i reads row o, so in_grad[i] = sum_k' out_grad[nbr[k', i]] @ W[K-1-k']^T); its filter gradient on the staged-rows kernel
     (csrc/spconv_wgrad_slab.h) over metadata the rulebook producers write directly in that kernel's address format;
   * strided layers on the tiled gather kernels over int32 tables built from the output side (rank-index lookups, no fill), their
-    input gradient over the transposed table, their filter gradient on the gather kernel (spconv_wgrad16_kernel).
+    input gradient over the transposed table, their filter gradient on the staged-rows kernel over metadata built from the layer's
+    table where no range can outgrow that metadata's 16-bit slots (strided_wgrad_route), else on the gather kernel
+    (spconv_wgrad16_kernel).
 
 BatchNorm (+ ReLU, + identity) stays `spconv/bn.py`'s two-launch pair per direction.  16-bit compute only (autocast, or 16-bit
 weights); anything else — fp32 training, rows not promised to be in linear order, a module tree that is not conv -> BN1d [-> ReLU] /
@@ -33,6 +35,68 @@ from . import fused, ops
 
 _ENABLED = os.environ.get("BEVAMD_SPCONV_FUSED_TRAIN", "1") != "0"
 _PAD_ROWS = 256     # feature buffers are allocated in whole 256-row blocks (the largest staged block), handed on as [:m] views
+
+
+_SLOT_LIMIT = 0xFFFE   # longest range the 16-bit slots of the staged-rows metadata hold (csrc/spconv_slab_meta.h: slab_emit clips there)
+
+
+def strided_slab_range_bound(Y, Z, block_rows, planes=1, pad_z=1):
+    """Upper bound R on hi - lo + 1, the input rows between the first and the last neighbour that one block of `block_rows`
+    consecutive output rows of a 3x3x3 stride-2 padding-1 convolution reads through one kernel plane kx, input and output rows in
+    ascending linear index, input grid [X, Y, Z]:  R = planes * Y * Z + 12 * block_rows + 5 * Z  (padding (1, 1, 0) on an odd Z,
+    the flagship's 64 -> 128 layer: 18 * block_rows).
+
+    Derivation.  hi - lo + 1 is the number of active input cells whose linear index lies between the two neighbours.  Output
+    (b, ox, oy, oz) reads input plane 2 ox - 1 + kx, lines 2 oy - 1 .. 2 oy + 1.  Let the block run from output o_a = (b_a, ox_a,
+    oy_a, ..) to o_b; every active output between them is one of its m <= block_rows rows, so an output plane strictly between
+    (b_a, ox_a) and (b_b, ox_b) ("interior") has all its m_o rows in the block.  The cells counted lie in the input planes from
+    x_a = 2 ox_a - 1 + kx (lines >= 2 oy_a - 1) to x_b = 2 ox_b - 1 + kx (lines <= 2 oy_b + 1).
+      (1) An active cell (x, y, z) makes output (o, y >> 1, z >> 1) active for every output plane o that reads plane x, and an
+          output has at most 4 such cells per input plane.  So a plane read by an interior output plane o holds <= 4 m_o cells; o
+          reads three planes: <= 12 rows of the block's interior planes in all.  (Padding 0 along z, Z odd: output oz reads cells
+          2 oz .. 2 oz + 2, every cell is read, cell z belongs to min(z >> 1, last oz) — the last output owns 3: 6 cells per
+          plane, 18 in all.  An even Z would leave the cells z = Z - 1 without an output, and is not admitted.)
+      (2) Every plane strictly between 2 ox_a + 1 and 2 ox_b - 1 (across samples: every plane of a sample in between, the planes
+          above 2 ox_a + 1 of sample b_a, those below 2 ox_b - 1 of sample b_b) is read by an interior output plane.  What is left
+          are x_a .. 2 ox_a + 1 and 2 ox_b - 1 .. x_b: four planes, three when ox_b = ox_a + 1.
+      (3) In x_a the cells whose output (ox_a, y >> 1, z >> 1) is a row of the block number <= 4 m_a; the others have
+          y >> 1 <= oy_a, i.e. sit in the lines 2 oy_a - 1 .. 2 oy_a + 1: <= 3 Z.  In x_b likewise <= 4 m_b + 2 Z (lines 2 oy_b,
+          2 oy_b + 1).  A block inside one output plane stops here: <= 4 m + 5 Z.
+      (4) The other left-over planes — kx = 0: 2 ox_a, 2 ox_a + 1; kx = 1: 2 ox_a + 1, 2 ox_b - 1; kx = 2: 2 ox_b - 1, 2 ox_b.
+          Plane 2 ox_a + 1 is also read by output plane ox_a + 1, plane 2 ox_b - 1 by ox_b - 1: interior (then (1) holds), or the
+          other end of the block — then the plane is x_b resp. x_a ((3) holds) for kx = 0 resp. 2, and ONE whole plane that both
+          ends share for kx = 1, whose outputs may all lie outside the block: <= Y Z.  Planes 2 ox_a (kx = 0) and 2 ox_b (kx = 2)
+          are read by the end plane alone: <= Y Z, one plane per kx.  Within a sample that is `planes` = 1.
+      (5) The seam between two samples of an EVEN X: the last input plane X - 1 is read by the last output plane alone.  With
+          o_a in that plane and a row of the next sample's output plane >= 1 in the block (its plane 0 holds < block_rows outputs),
+          kx = 0 spans the whole planes X - 2 and X - 1 of sample b_a: `planes` = 2, and a set that fills them reaches it.
+    Summed: rows <= 12 (m_int + m_a + m_b) + 5 Z + planes Y Z <= R.  A dense grid comes within about 8 block_rows + 5 Z of the
+    one-plane bound (a block that straddles two output planes reads ~4 cells per row and the plane in between)."""
+    return int(planes) * int(Y) * int(Z) + (12 if pad_z else 18) * int(block_rows) + 5 * int(Z)
+
+
+def strided_wgrad_route(shape, batch, block_rows, stride=(2, 2, 2), padding=(1, 1, 1)):
+    """How the filter gradient of a strided 3x3x3 layer over input grid `shape` may use the staged-rows kernel, whose metadata
+    drops the neighbours beyond _SLOT_LIMIT rows of a range:
+      "staged"   no set of voxels on this grid can overflow a range (strided_slab_range_bound at its worst case);
+      "checked"  only a seam between two samples could (case (5) of the bound: two completely filled x-planes at the end of a
+                 sample): the layer's metadata is built in front of the step's read-back, its status word travels with the row
+                 counts, and a step whose word is set takes the gather kernel for this layer (_Plan.resolve).  A pass that reads
+                 every status word up front (an encoder's first call, BEVAMD_SPCONV_CHECK=1) sees the same word earlier
+                 (fused.geometry_status in run_encoder): it hands such a step to the module path as a whole, like any other
+                 overflow, and keeps checking on the next call;
+      "gather"   a range inside one sample can overflow: the gather kernel (spconv_wgrad16) serves the layer."""
+    X, Y, Z = (int(s) for s in shape)
+    rows = int(block_rows) & 0xFFFF
+    pad_z = int(padding[2])
+    if tuple(stride) != (2, 2, 2) or tuple(padding[:2]) != (1, 1) or not (pad_z == 1 or (pad_z == 0 and Z % 2 == 1 and Z >= 3)):
+        return "gather"             # the bound is derived for these layers only
+    if strided_slab_range_bound(Y, Z, rows, 1, pad_z) >= _SLOT_LIMIT:
+        return "gather"
+    seam = int(batch) > 1 and X % 2 == 0
+    if seam and strided_slab_range_bound(Y, Z, rows, 2, pad_z) >= _SLOT_LIMIT:
+        return "checked"
+    return "staged"
 
 
 class _Lv:
@@ -93,6 +157,11 @@ class _Plan:
                 else:
                     L = _Layer(m, self, self.cur, None)
                     L.issue()
+                    if L.wg_checked:
+                        # in front of the read-back that carries its status word — on every pass, one that never runs a backward
+                        # (a training-mode forward under no_grad) included: one slab_build launch on the geometry stream ahead of
+                        # the step's sync, which before only issue_backward_products() made, behind the forward
+                        L.issue(forward=False)
                     nxt = _Lv(self.cur.level.downsample(m.kernel_size, m.stride, m.padding, wait=False, want_nbr=True)[0])
                     self.pending.append(nxt)
                     L.lv_out = nxt
@@ -112,9 +181,26 @@ class _Plan:
         """The step's ONE host sync: the row counts of every level a strided convolution produced, read on the geometry stream."""
         if not self.pending:
             return
+        # ... which also carries the status words of the strided layers whose staged-rows filter gradient is admitted on that
+        # condition (strided_wgrad_route "checked"): a set word = neighbours were dropped from this step's metadata, the layer's
+        # filter gradient takes the gather kernel over its table this step
+        checked = [L for L in self.layers if L.wg_checked and L.wg_code]
+        words = []
+        for L in checked:
+            lvl, key = L.lv_in.level, (tuple(L.conv.kernel_size), tuple(L.conv.stride), tuple(L.conv.padding), L.wg_code, "table")
+            if key not in lvl._down_slab:
+                # only a caller that drives the layers by hand gets here (advance() has built the metadata inside its prefetch
+                # bracket): built on demand, OUTSIDE that bracket on purpose — Level._fork() then orders the geometry stream
+                # behind what the main stream has issued, as for every product asked for in the middle of a pass
+                L.issue(forward=False)
+            words.append(lvl._down_slab[key][0].status)
         with self._on_geometry_stream():
-            host = torch.cat([lv.level.n_dev.reshape(1) for lv in self.pending]).cpu()
-        for lv, v in zip(self.pending, host.tolist()):
+            host = torch.cat([lv.level.n_dev.reshape(1) for lv in self.pending] + [w.reshape(1) for w in words]).cpu().tolist()
+            for L, w, v in zip(checked, words, host[len(self.pending):]):
+                if v:
+                    L.wg_code = 0
+                    w.zero_()               # the words live in a pool that is not re-zeroed per pass (fused._status_pool)
+        for lv, v in zip(self.pending, host):
             lv.n = int(v)
         self.pending = []
 
@@ -151,6 +237,7 @@ class _Layer:
         # channels (round 6: its gather-kernel filter gradient took 172 + 49 us and wanted a hash index + an int32 table of level 1
         # that nothing else reads; padded to 16 -> 16 it is the 23-us kernel of the other level-1 layers, the extra rows of dW dropped)
         self.wg_code = 0
+        self.wg_checked = False    # strided layers: the metadata's status word is read with the step's row counts (_Plan.resolve)
         self.wg_cin = self.cin
         if conv.subm and lvl.linear_order and tuple(conv.kernel_size) == (3, 3, 3) and lvl.allow_slab \
                 and (self.cin == self.cout or (self.cin < self.cout and self.cout == 16)):
@@ -161,9 +248,15 @@ class _Layer:
         elif (not conv.subm) and self.K == 27 and tuple(conv.kernel_size) == (3, 3, 3) and lvl.linear_order and lvl.allow_slab \
                 and os.environ.get("BEVAMD_SPCONV_WGRAD_SLAB_STRIDED", "1") != "0":
             # the strided 3x3x3 layers (16 -> 32, 32 -> 64, 64 -> 128): the same kernel over metadata built from the layer's table
+            # (taken only where a range cannot outgrow the metadata's 16-bit slots, or where the step checks it: strided_wgrad_route)
             lib = _capi.load()
-            if lib.bevamd_spconv_wgrad_slab_supported(ops._DT[plan.dtype], self.cin, self.cout):
-                self.wg_code = int(lib.bevamd_spconv_wgrad_slab_block_rows(self.cin))
+            if lib.bevamd_spconv_wgrad_slab_supported(ops._DT[plan.dtype], self.cin, self.cout) \
+                    and all(d == 1 for d in conv.dilation):
+                code = int(lib.bevamd_spconv_wgrad_slab_block_rows(self.cin))
+                route = strided_wgrad_route(lvl.shape, lvl.batch, code, conv.stride, conv.padding)
+                if route != "gather":
+                    self.wg_code = code
+                    self.wg_checked = route == "checked"
         self.nbr_t = None
         self.image = self.image_t = None     # forward / input-gradient filter images of this step (one batched launch: run_encoder)
 
