@@ -173,6 +173,9 @@ _EXT_SIGNATURES = {
     "bevamd_centerpoint_select": (I, [P, P, I, I, I, I, I, I, P, P, P, Z, P]),
     "bevamd_centerpoint_decode": (I, [P, P, P, I, I, I, I, I, P, P, I, I, P, P, c_float, I, c_float, I, P, P, P, P, P, P]),
     "bevamd_rotate_nms_segments": (I, [P, I, P, P, P, I, I, I, P, P, P, P, I, I, P, P, P]),
+    # head training targets
+    "bevamd_centerhead_targets": (I, [P, P, P, I, I, I, I, P, I, I, P, P, I, I, ctypes.c_double, I, I, P, P, P, P, P, P]),
+    "bevamd_heatmap_targets": (I, [P, P, P, I, I, I, I, I, P, P, I, I, ctypes.c_double, I, P, P, P]),
 }
 
 

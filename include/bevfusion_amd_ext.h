@@ -206,6 +206,47 @@ int bevamd_rotate_nms_segments(const float* boxes, int box_width, const int* lab
                                const float* task_scale, int pre_max_size, int post_max_size, unsigned char* keep,
                                int* seg_counts, void* stream);
 
+
+/* Training targets of the two heads: CenterHead.get_targets_single (mmdet3d/models/heads/bbox/centerpoint.py:432-582) and the
+ * dense heatmap of TransFusionHead.get_targets_single (transfusion.py:526-573), over core/utils/gaussian.py.  Nothing below
+ * synchronises the device or reads anything back.  LAUNCHES: bevamd_centerhead_targets 3 (zero, slots, draw),
+ * bevamd_heatmap_targets 2 (zero, draw), on `stream`, for ANY batch, num_rows and box contents; both can be captured in a graph.
+ * No workspace.  The heatmap is zeroed inside the call and every other output element is written on every call.
+ *
+ * Packed inputs: boxes [num_rows, box_dim] fp32 in the LiDAR layout (bottom centre x, y, z; dx, dy, dz; yaw; vx, vy when box_dim
+ *   is 9; 7: the velocity columns of anno_box are 0), labels [num_rows] int64, offsets [batch + 1] int32 ON THE DEVICE: sample b
+ *   owns the rows [offsets[b], offsets[b + 1]).  max_boxes_per_sample: the caller's HOST bound, 1 .. 1024 (more: 4, unsupported,
+ *   before any GPU work).  A sample with more rows than the bound (or whose offsets do not name a range of the arrays) produces
+ *   all-zero outputs and overflow[b] = 1; every other entry of overflow [batch] int32 is 0.
+ * pc_range, voxel_size: HOST, 2 floats each (the fp32 values of torch.tensor(train_cfg[...])); map_size: the feature map is
+ *   map_size x map_size (grid_size // out_size_factor; SQUARE only: the reference draws on a [size[1], size[0]] plane at
+ *   (row cell_x, column cell_y) and indexes it with cell_x * size[1] + cell_y, which agree only on square maps).
+ * Shared semantics, in the reference's fp32 operation order without FMA contraction and with correctly rounded divide / sqrt:
+ *   width = dx / voxel_size[0] / out_size_factor, length = dy / voxel_size[1] / out_size_factor; a box is skipped unless both are
+ *   > 0; radius = max(min_radius, int(gaussian_radius((length, width), gaussian_overlap))) as CPU fp32 torch evaluates it, the
+ *   Python-float constants formed in double and rounded to fp32; coor = (x - pc_range) / voxel_size / out_size_factor, the cell is
+ *   coor truncated toward zero (a coordinate in (-1, 0) lands in cell 0); a cell outside the map skips the box.  The Gaussian
+ *   exp(-(dx^2 + dy^2) / (2 sigma^2)), sigma = (2 radius + 1) / 6, is evaluated in double, cut below eps, rounded once to fp32 and
+ *   combined by maximum over the window clipped to the map, at row cell_x, column cell_y of the box's plane.
+ * bevamd_centerhead_targets: task t owns the labels [flag_t, flag_t + task_classes[t]) (HOST table, at most 16 tasks, 64 classes
+ *   in all); other labels, -1 included, are ignored.  Slot k of (task, sample) is the k-th box of the task in CLASS-MAJOR order,
+ *   stable within a class; only the first max_objs (the caller's max_objs * dense_reg) are processed; a skipped box leaves its
+ *   slot zero with mask 0.  heatmap: per task a contiguous [batch, task_classes[t], size, size] block, tasks in order;
+ *   anno_box [num_tasks, batch, max_objs, 10] = (coor_x - cell_x, coor_y - cell_y, z + dz * 0.5, dims (log with norm_bbox),
+ *   sin(yaw), cos(yaw), vx, vy), log / sin / cos rounded once from double; ind [num_tasks, batch, max_objs] int64 =
+ *   cell_x * size + cell_y; mask uint8.
+ * bevamd_heatmap_targets: heatmap [batch, num_classes, size, size], plane = label.  Where the reference is undefined (a centre
+ *   cell outside the map or a label outside [0, num_classes): its slices turn negative and index from the end) the box is SKIPPED. */
+int bevamd_centerhead_targets(const float* boxes, const long long* labels, const int* offsets, int num_rows, int box_dim,
+                              int batch, int max_boxes_per_sample, const int* task_classes, int num_tasks, int max_objs,
+                              const float* pc_range, const float* voxel_size, int out_size_factor, int map_size,
+                              double gaussian_overlap, int min_radius, int norm_bbox, float* heatmap, float* anno_box,
+                              long long* ind, unsigned char* mask, int* overflow, void* stream);
+int bevamd_heatmap_targets(const float* boxes, const long long* labels, const int* offsets, int num_rows, int box_dim, int batch,
+                           int max_boxes_per_sample, int num_classes, const float* pc_range, const float* voxel_size,
+                           int out_size_factor, int map_size, double gaussian_overlap, int min_radius, float* heatmap,
+                           int* overflow, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
