@@ -19,8 +19,10 @@ convolution waits on the event of the table it reads (`BEVAMD_SPCONV_GEOM_STREAM
 Reference semantics followed: SparseEncoder.forward (models/backbones/sparse_encoder.py:100-132), SparseBasicBlock
 .forward (ops/sparse_block.py:88-107), SparseConvolution.forward (ops/spconv/conv.py:118-223), BatchNorm1d eval.
 """
+import contextlib
 import ctypes
 import os
+from collections import namedtuple
 
 import torch
 from torch import nn
@@ -39,15 +41,30 @@ class NotThisCall(Exception):
     """This particular input is left to the module path (e.g. no voxels at all); the fused path stays enabled."""
 
 
+# ---- switches: every environment variable this path reads, each read ONCE, here (tools/ab.sh sets them per process) ----
+_GEOM_STREAM = os.environ.get("BEVAMD_SPCONV_GEOM_STREAM", "1") != "0"    # 0: rulebooks and convolutions on one stream
+_CHECK = os.environ.get("BEVAMD_SPCONV_CHECK", "0") == "1"               # read the geometry status words back after every fused forward (one sync)
+_SLAB = os.environ.get("BEVAMD_SPCONV_SLAB", "1") != "0"                 # 0: every layer stays on the gather kernels
+# "32:322133,64:642232": slab variant per channel width (16: the narrow SubM layers, -16: the narrow strided layer); tuning
+_SLAB_OVERRIDES = {int(c): int(v) for c, v in (item.split(":") for item in
+                                               filter(None, os.environ.get("BEVAMD_SPCONV_SLAB_VARIANTS", "").split(",")))}
 # How many convolutions ahead of the feature pass the rulebook chain is issued (see _Chain); -1: the whole chain up front.
 _CHAIN_LOOKAHEAD = int(os.environ.get("BEVAMD_SPCONV_CHAIN_LOOKAHEAD", "4"))
-# hold each strided layer's products behind the convolutions issued so far (see _Chain.advance)
-# (measured, off by default: 4.90 / 4.93 against 4.94 / 4.95 ms per 8-frame step, 0.98 against 0.96 ms on one frame)
-_CHAIN_HOLD = os.environ.get("BEVAMD_SPCONV_CHAIN_HOLD", "0") == "1"
-# skip a wait on a geometry-stream event the main stream is already ordered behind (tuning switch)
-_DEDUPE_WAITS = os.environ.get("BEVAMD_SPCONV_DEDUPE_WAITS", "1") != "0"
+
 _GEOM_STREAMS = {}
-_PREFETCHING = [False]   # inside prefetch_geometry: products are built behind the fork point, nothing of this pass runs on the main stream yet
+_PREFETCHING = [False]   # inside _prefetching(): products are built behind the fork point, nothing of this pass runs on the main stream yet
+
+
+@contextlib.contextmanager
+def _prefetching():
+    """Bracket around products issued ahead of their consumers: Level._fork() does nothing inside it.  Re-entrant."""
+    old = _PREFETCHING[0]
+    _PREFETCHING[0] = True
+    try:
+        yield
+    finally:
+        _PREFETCHING[0] = old
+
 
 # Per-layer profile (bench.py's `roofline_spconv`): set to a list and every fused convolution appends a record with HIP events
 # around its launch and, after a sync, its pair count.  None (default) = no overhead.  Only meaningful in eager passes.
@@ -60,7 +77,7 @@ LAYER_PROFILE_REPS = 1
 
 def geometry_stream(device):
     """The side stream rulebook construction runs on (one per device, created on first use); None when disabled."""
-    if os.environ.get("BEVAMD_SPCONV_GEOM_STREAM", "1") == "0":
+    if not _GEOM_STREAM:
         return None
     key = torch.device(device).index
     if key not in _GEOM_STREAMS:
@@ -72,10 +89,10 @@ class Level:
     """An active voxel set at one resolution: coordinates (capacity-sized), live count on the device, and an index
     that maps a cell to its row (hash for arbitrary row order, rank for ascending order).
 
-    `gstream` (optional): the stream every rulebook kernel of this level is launched on.  Products carry the event
-    recorded behind them; `subm_neighbors` / `downsample` make the CURRENT stream wait on it before handing them out.
-    Buffers are allocated by the caller's (current-stream) allocator; `run_encoder` joins the two streams before it
-    returns, so their reuse stays ordered."""
+    `gstream` (optional): the stream every rulebook kernel of this level is launched on.  Products live in ONE cache,
+    `(method name, arguments) -> (value, event recorded behind it)`; the methods that hand them out make the CURRENT stream wait
+    on that event (wait=True).  Buffers are allocated by the caller's (current-stream) allocator; `open_pass` joins the two
+    streams before the pass returns, so their reuse stays ordered."""
 
     def __init__(self, indices, n_cap, n_dev, batch, shape, gstream=None, linear_order=False, status_pool=None, allow_slab=True,
                  sync=None):
@@ -97,15 +114,9 @@ class Level:
         self.index_n_cap = 0
         self.gstream = gstream
         self.ready = None           # event behind the kernels that produced indices / n_dev / index (None: already ordered)
-        self._subm = {}
-        self._down = {}
-        self._slab = {}
-        self._down_slab = {}
+        self._products = {}
         self.linear_order = bool(linear_order)   # rows in ascending linear index (every set a strided convolution produced;
         #                                          level 1 when the caller vouches for it: voxelize(..., order="key"))
-        self.sorted_index = None    # (keys, x-plane directory): the set's own sorted-key index (ops.sorted_index_build)
-        self.sorted_status = None
-        self._sorted_ev = None
 
     @property
     def device(self):
@@ -146,16 +157,59 @@ class Level:
 
     def _await(self, ev):
         """Make the current stream wait for `ev` — unless it already waited, in this pass, for this or a LATER event of the geometry
-        stream (_DEDUPE_WAITS): the four layers of a level all ask for the same metadata, and every repeated wait is one more
-        cross-queue edge on a node of the captured graph."""
+        stream: the four layers of a level all ask for the same metadata, and every repeated wait is one more cross-queue edge on
+        a node of the captured graph (EXPERIMENTS.md B.14)."""
         if ev is None:
             return
         seq = getattr(ev, "_bevamd_seq", None)
-        if _DEDUPE_WAITS and seq is not None:
+        if seq is not None:
             if seq <= self._sync["awaited"]:
                 return
             self._sync["awaited"] = seq
         torch.cuda.current_stream().wait_event(ev)
+
+    # ---- the product cache ----
+    @staticmethod
+    def _key(kind, args):
+        return (kind,) + tuple(tuple(a) if isinstance(a, (list, tuple)) else a for a in args)
+
+    def _product(self, key, build, wait):
+        """The cached product `key`, built on the geometry stream (behind a fork) if it is not there yet."""
+        entry = self._products.get(key)
+        if entry is None:
+            self._fork()
+            value = build()
+            entry = self._products[key] = (value, self._mark())
+        if wait:
+            self._await(entry[1])
+        return entry[0]
+
+    def has(self, kind, *args):
+        """Whether the product the method `kind` hands out for `args` has been built; without `args`: any product of that method
+        (`lvl.has("subm_neighbors")`: an int32 SubM table of this level exists)."""
+        if args:
+            return self._key(kind, args) in self._products
+        return any(k[0] == kind for k in self._products)
+
+    def below(self):
+        """The level the (last) strided convolution over this set produced, None if there is none yet."""
+        out = None
+        for key, (value, _) in self._products.items():
+            if key[0] == "downsample":
+                out = value[0]
+        return out
+
+    def status_words(self):
+        """The device status words of this level's products (slab metadata, sorted-key index)."""
+        words = [v.status for k, (v, _) in self._products.items() if k[0] in ("subm_slab", "down_slab", "down_slab_from_table")]
+        if self.has("ensure_sorted"):
+            words.append(self.sorted_status)
+        return [w for w in words if w is not None]
+
+    def drop_events(self):
+        """The products are complete on the current stream: later consumers need no event and no geometry stream."""
+        self.ready = self.gstream = None
+        self._products = {k: (v[0], None) for k, v in self._products.items()}
 
     def ensure_index(self):
         if self.index is not None:
@@ -177,27 +231,27 @@ class Level:
         """Sorted-key index of a set in linear order (no hash insert, nothing to clear): built once, on the geometry stream."""
         if not self.linear_order:
             raise RuntimeError("sorted-key index of a voxel set that is not in linear order")
-        if self.sorted_index is None:
-            self._fork()
-            self.sorted_index, self.sorted_status = ops.sorted_index_build(self.indices, self.n_cap, self.n_dev, self.batch,
-                                                                           self.shape, stream_ptr=self._stream_ptr(),
-                                                                           status=self._status())
-            self._sorted_ev = self._mark()
-        if wait:
-            self._await(self._sorted_ev)
-        return self.sorted_index
+        return self._product(("ensure_sorted",), lambda: ops.sorted_index_build(
+            self.indices, self.n_cap, self.n_dev, self.batch, self.shape, stream_ptr=self._stream_ptr(), status=self._status()), wait)[0]
+
+    @property
+    def sorted_index(self):
+        """(keys, x-plane directory): the set's own sorted-key index (ops.sorted_index_build), None until ensure_sorted()."""
+        entry = self._products.get(("ensure_sorted",))
+        return None if entry is None else entry[0][0]
+
+    @property
+    def sorted_status(self):
+        entry = self._products.get(("ensure_sorted",))
+        return None if entry is None else entry[0][1]
 
     def use_sorted(self):
-        """Neighbour search of this set goes through its sorted-key index (level 1 in key order: it has no rank index);
-        BEVAMD_SPCONV_SORTED_ALL=1 extends that to the levels that do have one (tuning)."""
-        if not self.linear_order or not _SORTED:
-            return False
-        return self.index_kind != INDEX_RANK or _SORTED_ALL
+        """Neighbour search of this set goes through its sorted-key index: level 1 in key order, which has no rank index."""
+        return self.linear_order and self.index_kind != INDEX_RANK
 
     def _neighbors(self, out_indices, m_cap, m_dev, out_shape, ksize, stride, padding, subm):
         lib = _capi.load()
         self.ensure_index()
-        self._fork()
         dev = self.device
         K = ksize[0] * ksize[1] * ksize[2]
         nbr = torch.empty((K, max(m_cap, 1)), dtype=torch.int32, device=dev)
@@ -211,88 +265,71 @@ class Level:
 
     def subm_neighbors(self, ksize, wait=True):
         """nbr [K, n_cap] of a submanifold convolution over this set (built once per kernel size)."""
-        key = tuple(ksize)
-        if key not in self._subm:
-            nbr = self._neighbors(self.indices, self.n_cap, self.n_dev, self.shape, list(ksize), [1, 1, 1],
-                                  [k // 2 for k in ksize], True)
-            self._subm[key] = (nbr, self._mark())
-        nbr, ev = self._subm[key]
-        if wait:
-            self._await(ev)
-        return nbr
+        return self._product(self._key("subm_neighbors", (ksize,)), lambda: self._neighbors(
+            self.indices, self.n_cap, self.n_dev, self.shape, list(ksize), [1, 1, 1], [k // 2 for k in ksize], True), wait)
 
     def subm_slab(self, block_rows, wait=True):
         """Slab metadata (ops.SlabMeta) of the 3x3x3 SubM neighbour table, for `block_rows`-row blocks: built once, on the
-        geometry stream, behind the table it rewrites."""
-        if block_rows not in self._slab:
-            self._fork()
+        geometry stream."""
+        def build():
             if self.use_sorted():
                 self.ensure_sorted(wait=False)
-                meta = ops.slab_build_from_sorted(self.indices, self.n_cap, self.n_dev, self.batch, self.shape, self.shape,
+                return ops.slab_build_from_sorted(self.indices, self.n_cap, self.n_dev, self.batch, self.shape, self.shape,
                                                   [1, 1, 1], [1, 1, 1], True, self.sorted_index, self.n_cap, block_rows,
                                                   stream_ptr=self._stream_ptr(), status=self._status())
-            elif (3, 3, 3) in self._subm or not _SLAB_DIRECT:
+            if self.has("subm_neighbors", (3, 3, 3)):   # a profiled pass has built the int32 table: rewrite it
                 nbr = self.subm_neighbors((3, 3, 3), wait=False)
-                meta = ops.slab_build(nbr, self.n_cap, self.n_dev, block_rows, stream_ptr=self._stream_ptr(), status=self._status())
-            else:   # nobody asked for the int32 table: every row looks its neighbours up itself, 54 B per row written in all
-                self.ensure_index()
-                meta = ops.slab_build_from_index(self.indices, self.n_cap, self.n_dev, self.batch, self.shape, self.index_kind,
-                                                 self.index, self.index_n_cap, block_rows, stream_ptr=self._stream_ptr(),
-                                                 status=self._status())
-            self._slab[block_rows] = (meta, self._mark())
-        meta, ev = self._slab[block_rows]
-        if wait:
-            self._await(ev)
-        return meta
+                return ops.slab_build(nbr, self.n_cap, self.n_dev, block_rows, stream_ptr=self._stream_ptr(), status=self._status())
+            # nobody asked for the int32 table: every row looks its neighbours up itself, 54 B per row written in all
+            self.ensure_index()
+            return ops.slab_build_from_index(self.indices, self.n_cap, self.n_dev, self.batch, self.shape, self.index_kind,
+                                             self.index, self.index_n_cap, block_rows, stream_ptr=self._stream_ptr(),
+                                             status=self._status())
+
+        return self._product(("subm_slab", block_rows), build, wait)
 
     def down_slab(self, ksize, stride, padding, block_rows, wait=True):
         """Slab metadata of the strided 3x3x3 convolution (ksize, stride, padding) over this set, for `block_rows`-row blocks
         of OUTPUT rows: from the sorted-key index of this (input) set, behind the downsample that numbered the outputs."""
-        key = (tuple(ksize), tuple(stride), tuple(padding), block_rows)
-        if key not in self._down_slab:
+        def build():
             out, _ = self.downsample(ksize, stride, padding, wait=False, want_nbr=False)
             self.ensure_sorted(wait=False)
-            self._fork()
-            meta = ops.slab_build_from_sorted(out.indices, out.n_cap, out.n_dev, self.batch, self.shape, out.shape, list(stride),
+            return ops.slab_build_from_sorted(out.indices, out.n_cap, out.n_dev, self.batch, self.shape, out.shape, list(stride),
                                               list(padding), False, self.sorted_index, self.n_cap, block_rows,
                                               stream_ptr=self._stream_ptr(), status=self._status())
-            self._down_slab[key] = (meta, self._mark())
-        meta, ev = self._down_slab[key]
-        if wait:
-            self._await(ev)
-        return meta
+
+        return self._product(self._key("down_slab", (ksize, stride, padding, block_rows)), build, wait)
 
     def down_slab_from_table(self, ksize, stride, padding, block_rows, wait=True):
         """Slab metadata of the strided 3x3x3 convolution from its int32 neighbour table (ops.slab_build) — what the staged-rows
         filter gradient of a training step reads (spconv/fused_train.py; a layer that trains keeps its table anyway)."""
-        key = (tuple(ksize), tuple(stride), tuple(padding), block_rows, "table")
-        if key not in self._down_slab:
+        def build():
             out, nbr = self.downsample(ksize, stride, padding, wait=False, want_nbr=True)
-            self._fork()
-            meta = ops.slab_build(nbr, out.n_cap, out.n_dev, block_rows, stream_ptr=self._stream_ptr(), status=self._status())
-            self._down_slab[key] = (meta, self._mark())
-        meta, ev = self._down_slab[key]
-        if wait:
-            self._await(ev)
-        return meta
+            return ops.slab_build(nbr, out.n_cap, out.n_dev, block_rows, stream_ptr=self._stream_ptr(), status=self._status())
+
+        return self._product(self._key("down_slab_from_table", (ksize, stride, padding, block_rows)), build, wait)
 
     def downsample(self, ksize, stride, padding, wait=True, want_nbr=True):
         """(output Level with its rank index, nbr [K, cap_out]) of a strided convolution over this set.  want_nbr=False (the
         convolution reads slab metadata instead): the int32 neighbour table is not built, nbr is None — a later call that
         does want it (profiling a slab layer) builds it from the output side."""
-        key = (tuple(ksize), tuple(stride), tuple(padding))
-        if key in self._down:
-            out, nbr = self._down[key]
-            ev = None
-            if nbr is None and want_nbr:
-                nbr = self._neighbors(out.indices, out.n_cap, out.n_dev, out.shape, list(ksize), list(stride), list(padding), False)
-                self._down[key] = (out, nbr)
-                ev = self._mark()
-            if wait:
-                self._await(out.ready)
-                self._await(ev)
-            return out, nbr
-        self._fork()
+        key = self._key("downsample", (ksize, stride, padding))
+        fresh = key not in self._products
+        out, nbr = self._product(key, lambda: self._downsample(ksize, stride, padding, want_nbr), wait=False)
+        ev = None
+        if fresh:
+            out.ready = self._products[key][1]   # behind the downsample: indices, count, rank index and this conv's nbr are final
+        elif nbr is None and want_nbr:
+            self._fork()
+            nbr = self._neighbors(out.indices, out.n_cap, out.n_dev, out.shape, list(ksize), list(stride), list(padding), False)
+            self._products[key] = ((out, nbr), out.ready)
+            ev = self._mark()
+        if wait:
+            self._await(out.ready)
+            self._await(ev)
+        return out, nbr
+
+    def _downsample(self, ksize, stride, padding, want_nbr):
         lib = _capi.load()
         dev = self.device
         out_shape = ops.get_conv_output_size(self.shape, list(ksize), list(stride), list(padding), [1, 1, 1])
@@ -309,8 +346,8 @@ class Level:
         # The table of a strided layer that stays on the gather kernels: from the INPUT side inside bevamd_spconv_downsample (a
         # -1 fill of 27 * cap words, then every input scatters into the <= 8 outputs it feeds), or — when this (input) level owns a
         # rank index — from the OUTPUT side afterwards: every output row looks its 27 input cells up (8-byte loads that
-        # neighbouring rows share) and writes its column of the table once, coalesced, no fill (_DOWN_NBR_FROM_OUTPUTS)
-        from_outputs = want_nbr and _DOWN_NBR_FROM_OUTPUTS and self.index_kind == INDEX_RANK
+        # neighbouring rows share) and writes its column of the table once, coalesced, no fill (EXPERIMENTS.md B.4)
+        from_outputs = want_nbr and self.index_kind == INDEX_RANK
         nbr = torch.empty((K, cap), dtype=torch.int32, device=dev) if want_nbr and not from_outputs else None
         # A level in linear order that owns a lookup structure (rank index; level 1 in key order: the directory of its sorted-key
         # index) finds the inputs of a tile of output cells as ONE row range: the output bitmap is built in LDS, tile by tile — two
@@ -347,11 +384,19 @@ class Level:
         out.linear_order = True
         if from_outputs:
             nbr = self._neighbors(out_indices, cap, num_out, out_shape, list(ksize), list(stride), list(padding), False)
-        out.ready = self._mark()    # behind the downsample: indices, count, rank index and this conv's nbr are final
-        self._down[key] = (out, nbr)
-        if wait:
-            self._await(out.ready)
         return out, nbr
+
+    def forward_product(self, conv, route, wait=True):
+        """What the forward kernel of `conv` over this set reads on `route` (_route_for): (output Level, slab metadata | None,
+        int32 neighbour table | None).  wait=False issues it ahead of the layer (the rulebook chain), wait=True hands it out."""
+        ks, st, pd = conv.kernel_size, conv.stride, conv.padding
+        slab = route.kernel == "slab"
+        if conv.subm:
+            meta = self.subm_slab(route.block_rows, wait) if slab else None
+            # the slab kernels read their own metadata: the int32 table is only built for them when profiling (pair counts)
+            return self, meta, self.subm_neighbors(ks, wait) if route.want_nbr else None
+        out, nbr = self.downsample(ks, st, pd, wait=wait, want_nbr=route.want_nbr)
+        return out, self.down_slab(ks, st, pd, route.block_rows, wait) if slab else None, nbr
 
 
 class FusedTensor:
@@ -391,6 +436,25 @@ def folded(conv, bn, dtype):
     return val
 
 
+# ---- routes ---------------------------------------------------------------------------------------------------
+# What one convolution runs on: kernel "slab" | "gather"; variant: the slab code, or the gather tiling (_variant_for);
+# block_rows: ops.slab_block_rows(cin, variant) for slab, 0 for gather; want_nbr: the int32 neighbour table is needed (the gather
+# kernels read it; a profiled pass counts pairs in it).  Level.forward_product maps a route to the rulebook products it reads.
+_Route = namedtuple("_Route", "kernel variant block_rows want_nbr")
+
+
+def _route_for(conv, lvl, gather=False):
+    """The route of `conv` over `lvl` — the ONE place that decides it; the feature pass (_conv), the rulebook chain
+    (_geometry_steps) and the training layers (fused_train._Layer) only consume it.  gather=True: a layer that needs its int32
+    table whatever the tables say (the strided layers of a training step: their input gradient runs over its transpose)."""
+    cin, cout = conv.in_channels, conv.out_channels
+    variant = None if gather else _slab_variant_for(conv, lvl, cin, cout)
+    if variant is not None:
+        return _Route("slab", variant, ops.slab_block_rows(cin, variant), LAYER_PROFILE is not None)
+    K = conv.kernel_size[0] * conv.kernel_size[1] * conv.kernel_size[2]
+    return _Route("gather", _variant_for(_frames_equivalent(lvl), K, cin, cout), 0, True)
+
+
 # ---- module walkers ---------------------------------------------------------------------------------------
 def _conv(conv, x, bn=None, relu=False, residual=None):
     from .conv import SparseConvolution
@@ -410,42 +474,24 @@ def _conv(conv, x, bn=None, relu=False, residual=None):
     lvl = x.level
     if lvl.chain is not None:
         lvl.chain.before(conv)
-    slab_variant = _slab_variant_for(conv, lvl, cin, cout)
-    # a strided 3x3x3 layer that stays on the gather kernels can still read slot metadata (sorted-key search) instead of a table
-    slots_meta = slab_variant is None and _gather_reads_slots(conv, lvl)
-    want_nbr = (slab_variant is None and not slots_meta) or LAYER_PROFILE is not None
-    if conv.subm:
-        # the slab kernels read their own metadata: the int32 neighbour table is only built for them when profiling (pair counts)
-        nbr = lvl.subm_neighbors(conv.kernel_size) if want_nbr else None
-        out_lvl = lvl
-    else:
-        out_lvl, nbr = lvl.downsample(conv.kernel_size, conv.stride, conv.padding, want_nbr=want_nbr)
+    route = _route_for(conv, lvl)
+    out_lvl, meta, nbr = lvl.forward_product(conv, route)
     K = conv.kernel_size[0] * conv.kernel_size[1] * conv.kernel_size[2]
     out = torch.empty((out_lvl.n_cap, cout), dtype=dtype, device=x.features.device)
     rec = None
     if LAYER_PROFILE is not None:
         torch.cuda.synchronize()          # the rulebook chain (geometry stream) is out of the way: the events bracket the kernel
-        rec = dict(cin=cin, cout=cout, K=K, subm=bool(conv.subm),
-                   kernel="slab" if slab_variant is not None else "gather+slots" if slots_meta else "gather",
-                   variant=slab_variant if slab_variant is not None else _variant_for(_frames_equivalent(lvl), K, cin, cout),
+        rec = dict(cin=cin, cout=cout, K=K, subm=bool(conv.subm), kernel=route.kernel, variant=route.variant,
                    start=torch.cuda.Event(enable_timing=True), end=torch.cuda.Event(enable_timing=True),
                    n_in=lvl.n_dev, n_out=out_lvl.n_dev, n_in_cap=lvl.n_cap, n_out_cap=out_lvl.n_cap, nbr=nbr)
         rec["start"].record()
+    epilogue = dict(bias=bias, bn_scale=scale, bn_shift=shift, residual=residual, relu=relu, num_out_dev=out_lvl.n_dev, out=out,
+                    variant=route.variant)
     for _ in range(LAYER_PROFILE_REPS if rec is not None else 1):
-        if slab_variant is not None:
-            rows = ops.slab_block_rows(cin, slab_variant)
-            meta = lvl.subm_slab(rows) if conv.subm else lvl.down_slab(conv.kernel_size, conv.stride, conv.padding, rows)
-            ops.sparse_conv_slab(x.features, image, meta, out_lvl.n_cap, cin, cout, bias=bias, bn_scale=scale, bn_shift=shift,
-                                 residual=residual, relu=relu, num_out_dev=out_lvl.n_dev, out=out, variant=slab_variant)
-        elif slots_meta:
-            meta = lvl.down_slab(conv.kernel_size, conv.stride, conv.padding, _GATHER_SLOT_ROWS)
-            ops.sparse_conv_tiled_slots(x.features, image, meta, out_lvl.n_cap, cin, cout, bias=bias, bn_scale=scale, bn_shift=shift,
-                                        residual=residual, relu=relu, num_out_dev=out_lvl.n_dev, out=out,
-                                        variant=_variant_for(_frames_equivalent(lvl), K, cin, cout))
+        if route.kernel == "slab":
+            ops.sparse_conv_slab(x.features, image, meta, out_lvl.n_cap, cin, cout, **epilogue)
         else:
-            ops.sparse_conv_tiled(x.features, image, nbr, out_lvl.n_cap, K, cin, cout, bias=bias, bn_scale=scale, bn_shift=shift,
-                                  residual=residual, relu=relu, num_out_dev=out_lvl.n_dev, out=out,
-                                  variant=_variant_for(_frames_equivalent(lvl), K, cin, cout))
+            ops.sparse_conv_tiled(x.features, image, nbr, out_lvl.n_cap, K, cin, cout, **epilogue)
     if rec is not None:
         rec["end"].record()
         rec["reps"] = LAYER_PROFILE_REPS
@@ -475,60 +521,36 @@ def summarize_layer_profile(records, elem_bytes=2):
     return out
 
 
-# Tiling per layer shape when a step carries several frames.  The library's own choice (variant 0) is tuned on one frame's row
-# counts, where the 128-channel layers have fewer row blocks than the GPU has CUs and want the smallest tile; the live row count is
-# unknown to the host here (capacity launches), so the frame count stands in for it.  tools/sweep_spconv.py --frames 8:
-# 128->128 228 -> 194 us, 64->128 128 -> 102 us, 32->64 153 -> 145 us, 32->32 274 -> 266 us, 64->64 251 -> 246 us
-# (A/B on one box, 8 frames: LiDAR branch 6.11-6.18 -> 5.91-5.94 ms; entries for the 5->16 and 16->32 layers, 10-16 % faster
-# in isolation, changed nothing inside the graph and were left out).
+# ---- routing tables (the measurements behind every constant: profiles/EXPERIMENTS.md D.18) -----------------------------------
+# Gather tiling per (padded cin, cout) when a step carries several frames.  The library's own choice (variant 0) is tuned on one
+# frame's row counts; the live row count is unknown to the host (capacity launches), so the frame count stands in for it.
 _BATCHED_VARIANTS = {(32, 32): 2213, (32, 64): 2211, (64, 64): 2221, (64, 128): 2211, (128, 128): 2221}
 
-
-# Slab (staged-rows) kernels for the 3x3x3 SubM layers of the sorted levels (csrc/spconv_slab*.h): BEVAMD_SPCONV_SLAB=0 keeps
-# the gather kernels; BEVAMD_SPCONV_SLAB_VARIANTS="32:322133,64:642232" overrides the per-width variant (tuning).  Codes:
-# xxxxxx = filter staged in LDS (spconv_slab.h), 1xxxxxx = filter fragments in registers (spconv_slab_regw.h), 2xxxxxx = the same,
-# persistent (spconv_slab_persist.h).  Measured (tools/sweep_spconv.py --slab, profiles/r02_slab_sweep_b{1,8}_v3.txt), 8 frames,
-# 32 / 64 / 128 channels: 186 / 183 / 151 us against 290 / 242 / 193 us of the gather kernels (first cut: 211 / 198 / 164); one
-# frame: 26.7 / 30.8 us against 41 / 35.8 us, 128 channels 38.5-40 against 38.8 us (188 blocks on 256 CUs) -> those layers switch
-# over from 4 frames per step.  The persistent 32-channel kernel was only measured at 8 frames: smaller batches keep its one-block twin.
-# Narrow layers (cin padded to 8 | 16: csrc/spconv_slab_small.h) on a level in linear order — level 1 when the voxelizer wrote
-# its rows in key order: 3000256 = 256-row blocks (the SubM layers share one metadata set); the strided 16 -> 32 convolution:
-# 3100128 = 128-row blocks, BOTH output tiles in one wave (round 5: these kernels are bound by the LDS pipe, and with the two tiles
-# on two waves — 3000128, 8-wave workgroups — every operand fragment was read from LDS twice: LiDAR branch alone 3.54 -> 3.45 ms).
-_CHECK = os.environ.get("BEVAMD_SPCONV_CHECK", "0") == "1"   # read the geometry status words back after every fused forward (one sync)
+# Slab (staged-rows) kernels for the 3x3x3 layers of levels in linear order (csrc/spconv_slab*.h).  Codes: xxxxxx = filter staged
+# in LDS (spconv_slab.h), 1xxxxxx = filter fragments in registers (spconv_slab_regw.h), 2xxxxxx = the same, persistent
+# (spconv_slab_persist.h), 3xxxxxx = narrow rows (spconv_slab_small.h), 4xxxxxx = filter-stationary (spconv_slab_fstat*.h).
+# Narrow layers (cin padded to 8 | 16) of a level searched through its sorted-key index — level 1 when the voxelizer wrote its rows
+# in key order: the SubM layers share one set of 256-row metadata; the strided 16 -> 32 layer takes 128-row blocks with both output
+# tiles in one wave.
 _SLAB_NARROW_SUBM = 3000256
 _SLAB_NARROW_STRIDED = 3100128
-_SORTED = os.environ.get("BEVAMD_SPCONV_SORTED", "1") != "0"          # sorted-key neighbour search on levels without a rank index
-_SORTED_ALL = os.environ.get("BEVAMD_SPCONV_SORTED_ALL", "0") == "1"  # ... and on those that have one (tuning)
-# 32 channels from 4 frames: the filter-stationary kernel (spconv_slab_fstat.h; 64-row blocks, baked slots): 159 us isolated against 190
-# of the persistent register-ring kernel 2324410, 5.58-5.60 against 5.77-5.78 ms per 8-frame step on the same box (its results
-# agree with the other kernels' to fp32 rounding, not bit for bit: v_mfma_32x32x16 sums 16 channels per step)
-# Round 5: 64 channels on the register-filter kernel with BAKED slot metadata (1644228: the fragment address is one v_xad_u32;
-# 189-193 -> 172-174 us per layer at 8 frames, 29.9 -> 28.2 at one; the same flag buys nothing at 128 channels: 154-157 either way);
-# 128 channels below 4 frames: 64-row blocks (1642220: one frame's level 4 is 188 blocks of 128 rows on 256 CUs; 39.5 -> 34.0 us,
-# gather kernel 38.8) — the kernel reads the filter-stationary kernels' baked 64-row metadata (EXPERIMENTS.md C.3: the "epilogue
-# bug" of B.17 was that metadata format read as raw slots).
-# Round 6: 32 channels on the filter-stationary WAVE-PAIR kernel (spconv_slab_fstat2.h, 4100128: two waves per SIMD split the input
-# channels, same baked metadata as 4000112).  One box, 8 frames, the encoder's epilogues: 139.7 / 149.8 / 154.3 us (BN + ReLU / + residual /
-# + device-side row count) against 167.0 / 171.9 / 173.6 of the one-wave kernel; inside the HIP graph 141-145 against 161-170 us per
-# layer.  The 8-frame step does not move (4.32-4.36 ms either way, three interleaved pairs of 200 steps: those layers run beside bev_pool
-# and the next batch's rulebook chain, and the three together are bound by what they share), the 4-frame step does: 2.36-2.37 against
-# 2.40-2.41 ms.  Two waves per SIMD leave room for a neighbour: with a rulebook kernel of the next levels beside it (the encoder's own
-# geometry stream under --overlap none) a layer takes 250 us where the one-wave kernel, whose 469-register waves fill the SIMDs, took
-# 170 and let the rulebook kernel wait instead — the LiDAR branch alone is 30 us slower for it (3.46 against 3.43 ms), every shared
-# schedule (ahead, lidar) is not (EXPERIMENTS D.12).
+# cin == cout SubM layers: 32 channels on the filter-stationary wave-pair kernel, 64 on the register-filter kernel with baked slot
+# metadata, 128 on the register-filter kernel ...
 _SLAB_DEFAULT = {32: 4100128, 64: 1644228, 128: 1644220}
-_SLAB_DEFAULT_SMALL_BATCH = {32: 1322410, 128: 1642220}   # below _SLAB_SMALL_BATCH_BELOW frames per step
-# 32 channels: the wave-pair kernel from TWO frames on (one box, encoder epilogues + device-side row count, 1 / 2 / 3 frames:
-# 1322410 29.6 / 53.2 / 74.2 us, 4000112 30.8 / 50.3 / 67.2, 4100128 29.2 / 43.5 / 58.8); 128 channels: 64-row blocks below 2.5 frames
-# (same box, 1 / 2 / 3 / 4 frames: 1642220 34.4 / 54.7 / 85.5 / 102.2 us, 1644220 40.4 / 56.6 / 79.9 / 93.4; 3.5 until round 6)
+# ... and below _SLAB_SMALL_BATCH_BELOW frames per step: 32 channels on the one-block register-ring kernel, 128 on 64-row blocks
+# (one frame's level 4 is fewer 128-row blocks than the GPU has CUs)
+_SLAB_DEFAULT_SMALL_BATCH = {32: 1322410, 128: 1642220}
 _SLAB_SMALL_BATCH_BELOW = {32: 1.5, 128: 2.5}
-_SLAB_MIN_BATCH = {}
+_SLAB_MIN_FRAMES = 0.5     # below half a frame's rows the cin == cout layers stay on the gather kernels
 # The same decisions in LIVE ROWS (8 sparse frames are not 8 capped ones).  The tilings were measured on
 # capped flagship frames (160 k voxels each), so "frames" = live level-1 rows / 160 k.  The host does not know the row count on the
 # sync-free path: the encoder's FIRST eager call at a batch size reads it back once (_frames_hint), every later call at that batch
 # size — graph captures included — uses the same figure, so that a replayed graph and its eager warm-up run the same kernels.
 _ROWS_PER_FLAGSHIP_FRAME = 160000
+# output set of a strided layer over a level in linear order: bitmap tiles in LDS from contiguous input row ranges
+# (bevamd_spconv_downsample_sorted; False: the byte map of bevamd_spconv_downsample, which serves every other level — a test flips
+# this to compare the two)
+_DOWN_SORTED = True
 
 
 def _frames_hint(enc, batch_size, n_rows, num_voxels):
@@ -551,43 +573,54 @@ def _frames_hint(enc, batch_size, n_rows, num_voxels):
 def _frames_equivalent(lvl):
     """Frames per step as the tilings understand them: from the live row count when it is known, else the batch size."""
     return float(lvl.batch) if lvl.frames_hint is None else lvl.frames_hint
-# BEVAMD_SPCONV_SLAB_DIRECT=0: build the slab metadata from the int32 neighbour table instead of straight from the rank index
-_SLAB_DIRECT = os.environ.get("BEVAMD_SPCONV_SLAB_DIRECT", "1") != "0"
-
-
-def _slab_overrides():
-    spec = os.environ.get("BEVAMD_SPCONV_SLAB_VARIANTS", "")
-    out = {}
-    for item in filter(None, spec.split(",")):
-        c, v = item.split(":")
-        out[int(c)] = int(v)
-    return out
 
 
 def _narrow_variant_for(conv, lvl, cin, cout):
     """Variant of the narrow-row slab kernels for this layer, None if it does not apply (3x3x3, cin <= 16, cout 16 | 32, input
     level in linear order with a sorted-key index)."""
-    if os.environ.get("BEVAMD_SPCONV_SLAB_NARROW", "1") == "0" or not lvl.use_sorted():
+    if not lvl.use_sorted():
         return None
     if not (cout in (16, 32) and (cout == 16 or cin > 8)):
         return None
-    overrides = _slab_overrides()
     if conv.subm:
-        variant = overrides.get(16, _SLAB_NARROW_SUBM)
+        variant = _SLAB_OVERRIDES.get(16, _SLAB_NARROW_SUBM)
         rows = ops.slab_block_rows(cin, variant)
         return variant if rows and ops.slab_grid_ok(lvl.shape, rows) else None
-    variant = overrides.get(-16, _SLAB_NARROW_STRIDED)
-    if not ops.slab_block_rows(cin, variant) and -16 not in overrides:
+    variant = _SLAB_OVERRIDES.get(-16, _SLAB_NARROW_STRIDED)
+    if not ops.slab_block_rows(cin, variant) and -16 not in _SLAB_OVERRIDES:
         variant = 3000128          # cin <= 8 -> 16: the both-tiles-in-one-wave shape (3100128) is built for 16 -> 32 only (ADVICE r5)
     return variant if ops.slab_block_rows(cin, variant) else None
 
 
-# neighbour table of the strided gather layers from the output side (rank-index lookups, no fill); 0 = from the input side
-_DOWN_NBR_FROM_OUTPUTS = os.environ.get("BEVAMD_SPCONV_DOWN_NBR", "outputs") != "inputs"
-# output set of a strided layer over a level in linear order: bitmap tiles in LDS from contiguous input row ranges (0: byte map)
-_DOWN_SORTED = os.environ.get("BEVAMD_SPCONV_DOWN_SORTED", "1") != "0"
+def _slab_variant_for(conv, lvl, cin, cout):
+    """Slab variant of `conv` over `lvl`, None: the layer stays on the gather kernels."""
+    if not _SLAB or not lvl.allow_slab:
+        return None
+    if tuple(conv.kernel_size) != (3, 3, 3) or not lvl.linear_order:
+        return None
+    if ops.padded_channels(cin) <= 16:
+        return _narrow_variant_for(conv, lvl, cin, cout)
+    if not (conv.subm and cin == cout):
+        return None
+    frames = _frames_equivalent(lvl)
+    if cin not in _SLAB_DEFAULT or frames < _SLAB_MIN_FRAMES:
+        return None
+    default = _SLAB_DEFAULT_SMALL_BATCH[cin] if frames < _SLAB_SMALL_BATCH_BELOW.get(cin, 0.0) else _SLAB_DEFAULT[cin]
+    variant = _SLAB_OVERRIDES.get(cin, default)
+    rows = ops.slab_block_rows(cin, variant)
+    if rows == 0 or not ops.slab_grid_ok(lvl.shape, rows):
+        return None
+    return variant
+
+
+def _variant_for(batch, K, cin, cout):
+    """Gather tiling.  `batch`: frames per step, or the frames-equivalent of the level's live rows (_frames_equivalent)."""
+    if batch >= 5.5 and K == 27:   # measured neutral at 4 frames, +4 % at 8
+        return _BATCHED_VARIANTS.get((ops.padded_channels(cin), cout), 0)
+    return 0
+
+
 _STATUS_WORDS = 64
-_STATUS_POOL = os.environ.get("BEVAMD_SPCONV_STATUS_POOL", "1") != "0"
 _STATUS_POOLS = {}
 
 
@@ -597,8 +630,6 @@ def _status_pool(dev):
     pass): the kernels only ever OR bits into a word on an error, nobody looks at the words of a pass that is not checked, and a
     checked pass clears what it reads.  The first pass on a device that happens to be a graph capture gets a tensor of its own
     (allocated and zeroed inside the capture, not kept)."""
-    if not _STATUS_POOL:
-        return None
     key = torch.device(dev).index
     if key not in _STATUS_POOLS:
         words = torch.zeros(_STATUS_WORDS, dtype=torch.int32, device=dev)
@@ -606,46 +637,6 @@ def _status_pool(dev):
             return [words, 0]
         _STATUS_POOLS[key] = words
     return [_STATUS_POOLS[key], 0]
-_PAD_CAST = os.environ.get("BEVAMD_SPCONV_PAD_CAST", "1") != "0"
-_GATHER_SLOT_ROWS = 128
-# measured at 8 frames and NOT the default: LiDAR branch 3.94 ms with it against 3.83 ms with the int32 tables — the 2-byte slot
-# decode makes the gather kernels 6-13 % slower (196 / 130 us against 185 / 115) and the extra sorted-key searches (128 + 60 us)
-# run under the level-2 layers, which is worth more than the 0.32 ms of table kernels they replace
-_GATHER_SLOTS = os.environ.get("BEVAMD_SPCONV_GATHER_SLOTS", "0") == "1"
-
-
-def _gather_reads_slots(conv, lvl):
-    """Strided 3x3x3 layers left on the gather kernels (32 -> 64, 64 -> 128: their input ranges are too long to stage) read slot
-    metadata built by sorted-key search from the input level instead of an int32 table that has to be cleared and scattered."""
-    return (_GATHER_SLOTS and _SORTED and lvl.allow_slab and not conv.subm and tuple(conv.kernel_size) == (3, 3, 3)
-            and lvl.linear_order)
-
-
-def _slab_variant_for(conv, lvl, cin, cout):
-    if os.environ.get("BEVAMD_SPCONV_SLAB", "1") == "0" or not lvl.allow_slab:
-        return None
-    if tuple(conv.kernel_size) != (3, 3, 3) or not lvl.linear_order:
-        return None
-    if ops.padded_channels(cin) <= 16:
-        return _narrow_variant_for(conv, lvl, cin, cout)
-    if not (conv.subm and cin == cout):
-        return None
-    frames = _frames_equivalent(lvl)
-    if cin not in _SLAB_DEFAULT or frames < _SLAB_MIN_BATCH.get(cin, 1) - 0.5:
-        return None
-    default = _SLAB_DEFAULT_SMALL_BATCH[cin] if frames < _SLAB_SMALL_BATCH_BELOW.get(cin, 0.0) else _SLAB_DEFAULT[cin]
-    variant = _slab_overrides().get(cin, default)
-    rows = ops.slab_block_rows(cin, variant)
-    if rows == 0 or not ops.slab_grid_ok(lvl.shape, rows):
-        return None
-    return variant
-
-
-def _variant_for(batch, K, cin, cout):
-    """`batch`: frames per step, or the frames-equivalent of the level's live rows (_frames_equivalent)."""
-    if batch >= 5.5 and K == 27:   # measured neutral at 4 frames (3.15 vs 3.17 ms per step), +4 % at 8
-        return _BATCHED_VARIANTS.get((ops.padded_channels(cin), cout), 0)
-    return 0
 
 
 def _sequential(seq, x):
@@ -723,18 +714,15 @@ def encoder_supported(enc, voxel_features):
     return unsupported_reason(enc, voxel_features) is None
 
 
-@torch.no_grad()
-def prepare_geometry(enc, coors, batch_size, num_voxels=None, coors_order=None, allow_slab=True):
-    """Everything of `run_encoder` that depends on voxel COORDINATES only — hash index, every level's active set, neighbour
-    tables, slab metadata — issued on the current stream (and finished there: the geometry stream, if any, is joined back).
-    Returns the level-1 `Level` holding the products; pass it to `SparseEncoder.forward(..., geometry=level)` /
-    `run_encoder(..., geometry=level)`.  Lets a caller run the rulebook chain (latency-bound integer kernels) underneath
-    something else — bench.py runs it, with the voxelizer, beside the HBM-bound camera branch — instead of underneath the
-    encoder's own convolutions."""
+# ---- one pass -------------------------------------------------------------------------------------------------
+@contextlib.contextmanager
+def open_pass(enc, coors, batch_size, num_voxels=None, linear_order=False, allow_slab=True, frames_hint=None):
+    """One pass over `coors` [N, 4] (+ the device-side live row count `num_voxels`): forks the geometry stream off the current one
+    (coordinates / count are final, recycled buffers are quiescent), yields the level-1 Level, and joins the two streams on the way
+    out, so that whatever follows on the current stream is ordered behind the geometry kernels.  `frames_hint`: the caller's own
+    frames-equivalent (a training step knows its row count); None: this encoder's measured figure (_frames_hint)."""
     coors = coors.int().contiguous()
     n = coors.shape[0]
-    if n == 0:
-        raise NotThisCall("empty input")
     if num_voxels is not None:
         num_voxels = num_voxels.reshape(-1)[:1].int().contiguous()
     dev = coors.device
@@ -743,37 +731,60 @@ def prepare_geometry(enc, coors, batch_size, num_voxels=None, coors_order=None, 
     pool = _status_pool(dev)
     if g is not None:
         g.wait_stream(main)
-    lvl = Level(coors, n, num_voxels, batch_size, enc.sparse_shape, gstream=g, linear_order=_is_linear(coors_order), status_pool=pool,
+    lvl = Level(coors, n, num_voxels, batch_size, enc.sparse_shape, gstream=g, linear_order=linear_order, status_pool=pool,
                 allow_slab=allow_slab)
-    lvl.frames_hint = _frames_hint(enc, int(batch_size), n, num_voxels)
+    lvl.frames_hint = _frames_hint(enc, int(batch_size), n, num_voxels) if frames_hint is None else frames_hint
     try:
-        prefetch_geometry(enc, lvl)
+        yield lvl
     finally:
         if g is not None:
             main.wait_stream(g)
-    # the products are complete on `main` from here on: later consumers need no per-product event
-    _drop_events(lvl)
+
+
+def _checked_pass(enc, once, coors_order, allow_slab, every_call=False):
+    """result of `once(coors_order, allow_slab) -> (result, level-1 Level)`, one complete (joined) pass — re-run once with the
+    overrides of _first_call_check when an encoder's first eager call finds a status word set.  every_call: a pass that is not
+    the first one reads the words too, and raises."""
+    result, lvl = once(coors_order, allow_slab)
     redo = _first_call_check(enc, lvl)
     if redo is not None:
-        lvl = prepare_geometry(enc, coors, batch_size, num_voxels=num_voxels, **dict(dict(coors_order=coors_order, allow_slab=allow_slab), **redo))
+        result = _checked_pass(enc, once, **dict(dict(coors_order=coors_order, allow_slab=allow_slab), **redo))
         enc.__dict__["_bevamd_geometry_checked"] = False   # the clean re-run does not vouch for the caller's next input
-    return lvl
+    elif every_call:
+        bits = geometry_status(lvl)
+        if bits:
+            raise RuntimeError(f"SparseEncoder fused path: geometry status {bits:#x} (1: slab range overflow, 2: coordinates "
+                               "passed with coors_order='linear' are not in ascending linear index)")
+    return result
 
 
-def _drop_events(lvl):
-    seen = set()
-    while lvl is not None and id(lvl) not in seen:
-        seen.add(id(lvl))
-        lvl.ready = None
-        lvl.gstream = None
-        lvl._subm = {k: (v[0], None) for k, v in lvl._subm.items()}
-        lvl._slab = {k: (v[0], None) for k, v in lvl._slab.items()}
-        lvl._down_slab = {k: (v[0], None) for k, v in lvl._down_slab.items()}
-        lvl._sorted_ev = None
-        nxt = None
-        for out, _ in lvl._down.values():
-            nxt = out
-        lvl = nxt
+@torch.no_grad()
+def prepare_geometry(enc, coors, batch_size, num_voxels=None, coors_order=None, allow_slab=True):
+    """Everything of `run_encoder` that depends on voxel COORDINATES only — hash index, every level's active set, neighbour
+    tables, slab metadata — issued on the current stream (and finished there: the geometry stream, if any, is joined back).
+    Returns the level-1 `Level` holding the products; pass it to `SparseEncoder.forward(..., geometry=level)` /
+    `run_encoder(..., geometry=level)`.  Lets a caller run the rulebook chain (latency-bound integer kernels) underneath
+    something else — bench.py runs it, with the voxelizer, beside the HBM-bound camera branch — instead of underneath the
+    encoder's own convolutions."""
+    if coors.shape[0] == 0:
+        raise NotThisCall("empty input")
+
+    def once(coors_order, allow_slab):
+        with open_pass(enc, coors, batch_size, num_voxels, _is_linear(coors_order), allow_slab) as lvl:
+            prefetch_geometry(enc, lvl)
+        # the products are complete on the current stream from here on: later consumers need no per-product event
+        for each in _levels(lvl):
+            each.drop_events()
+        return lvl, lvl
+
+    return _checked_pass(enc, once, coors_order, allow_slab)
+
+
+def _levels(lvl):
+    """`lvl` and the levels the strided convolutions built below it, top down."""
+    while lvl is not None:
+        yield lvl
+        lvl = lvl.below()
 
 
 def _first_call_check(enc, lvl):
@@ -816,23 +827,22 @@ def geometry_status(lvl):
     """OR of the device status words of every structure built for `lvl` and the levels below it (one host sync; tests and
     BEVAMD_SPCONV_CHECK=1): bit 0 = a slab range overflowed its 16-bit slots, bit 1 = rows promised to be in linear order
     were not."""
-    bits, seen = 0, set()
-    while lvl is not None and id(lvl) not in seen:
-        seen.add(id(lvl))
-        words = [m.status for m, _ in list(lvl._slab.values()) + list(lvl._down_slab.values())]
-        if lvl.sorted_status is not None:
-            words.append(lvl.sorted_status)
-        for wd in words:
-            if wd is not None:
-                v = int(wd.item())
-                if v:
-                    bits |= v
-                    wd.zero_()      # the words live in a per-device pool that is not re-zeroed per pass (_status_pool)
-        nxt = None
-        for out, _ in lvl._down.values():
-            nxt = out
-        lvl = nxt
+    bits = 0
+    for each in _levels(lvl):
+        for wd in each.status_words():
+            v = int(wd.item())
+            if v:
+                bits |= v
+                wd.zero_()      # the words live in a per-device pool that is not re-zeroed per pass (_status_pool)
     return bits
+
+
+def _features_pass(enc, feats, lvl):
+    x = FusedTensor(feats, lvl)
+    x = _sequential(enc.conv_input, x)
+    x = _sequential(enc.encoder_layers, x)
+    x = _sequential(enc.conv_out, x)
+    return dense_bev(x)
 
 
 def run_encoder(enc, voxel_features, coors, batch_size, num_voxels=None, geometry=None, coors_order=None, allow_slab=True):
@@ -850,7 +860,7 @@ def run_encoder(enc, voxel_features, coors, batch_size, num_voxels=None, geometr
         feats = voxel_features      # the voxelizer already wrote the padded 16-bit rows (voxelize_batch_device(encoder_rows=...))
     elif voxel_features.shape[1] != cin:
         raise RuntimeError(f"run_encoder: voxel_features has {voxel_features.shape[1]} columns, the encoder reads {cin}")
-    elif _PAD_CAST and voxel_features.dtype == torch.float32 and voxel_features.is_contiguous():
+    elif voxel_features.dtype == torch.float32 and voxel_features.is_contiguous():
         feats = torch.empty((n, pitch), dtype=dtype, device=voxel_features.device)
         with torch.cuda.device(voxel_features.device):
             rc = _capi.load().bevamd_spconv_pad_cast_rows(_capi.ptr(voxel_features), n, cin, pitch, ops._dtype_code(feats),
@@ -862,49 +872,18 @@ def run_encoder(enc, voxel_features, coors, batch_size, num_voxels=None, geometr
     if geometry is not None:
         if geometry.n_cap != n or geometry.batch != int(batch_size):
             raise RuntimeError("run_encoder: `geometry` was prepared for other inputs")
-        x = FusedTensor(feats, geometry)
-        x = _sequential(enc.conv_input, x)
-        x = _sequential(enc.encoder_layers, x)
-        x = _sequential(enc.conv_out, x)
-        return dense_bev(x)
-    coors = coors.int().contiguous()
-    if num_voxels is not None:
-        num_voxels = num_voxels.reshape(-1)[:1].int().contiguous()
-    dev = voxel_features.device
-    g = geometry_stream(dev)
-    main = torch.cuda.current_stream(dev)
-    pool = _status_pool(dev)
-    if g is not None:
-        g.wait_stream(main)       # fork: coordinates / count are final, recycled buffers are quiescent
-    lvl = Level(coors, n, num_voxels, batch_size, enc.sparse_shape, gstream=g, linear_order=_is_linear(coors_order), status_pool=pool,
-                allow_slab=allow_slab)
-    lvl.frames_hint = _frames_hint(enc, int(batch_size), n, num_voxels)
-    redo = None
-    try:
-        if g is not None:
-            if _CHAIN_LOOKAHEAD < 0:
-                prefetch_geometry(enc, lvl)
-            else:
-                lvl.chain = _Chain(enc, lvl, _CHAIN_LOOKAHEAD)
-        x = FusedTensor(feats, lvl)
-        x = _sequential(enc.conv_input, x)
-        x = _sequential(enc.encoder_layers, x)
-        x = _sequential(enc.conv_out, x)
-        out = dense_bev(x)
-        redo = _first_call_check(enc, lvl)
-        if redo is None and _CHECK:
-            bits = geometry_status(lvl)
-            if bits:
-                raise RuntimeError(f"SparseEncoder fused path: geometry status {bits:#x} (1: slab range overflow, 2: coordinates "
-                                   "passed with coors_order='linear' are not in ascending linear index)")
-    finally:
-        if g is not None:
-            main.wait_stream(g)   # join: whatever follows on this stream is ordered behind the geometry kernels
-    if redo is not None:
-        out = run_encoder(enc, voxel_features, coors, batch_size, num_voxels=num_voxels,
-                          **dict(dict(coors_order=coors_order, allow_slab=allow_slab), **redo))
-        enc.__dict__["_bevamd_geometry_checked"] = False   # the clean re-run does not vouch for the caller's next input
-    return out
+        return _features_pass(enc, feats, geometry)
+
+    def once(coors_order, allow_slab):
+        with open_pass(enc, coors, batch_size, num_voxels, _is_linear(coors_order), allow_slab) as lvl:
+            if lvl.gstream is not None:
+                if _CHAIN_LOOKAHEAD < 0:
+                    prefetch_geometry(enc, lvl)
+                else:
+                    lvl.chain = _Chain(enc, lvl, _CHAIN_LOOKAHEAD)
+            return _features_pass(enc, feats, lvl), lvl
+
+    return _checked_pass(enc, once, coors_order, allow_slab, every_call=_CHECK)
 
 
 def prefetch_geometry(enc, lvl):
@@ -912,12 +891,9 @@ def prefetch_geometry(enc, lvl):
     it: hash index, SubM neighbour tables and downsamples of every level.  The feature pass then finds each product in
     its Level's cache and waits on its event only.  A tree whose module order differs from its execution order merely
     builds some tables later, on demand."""
-    _PREFETCHING[0] = True
-    try:
+    with _prefetching():
         for _ in _geometry_steps(enc, lvl):
             pass
-    finally:
-        _PREFETCHING[0] = False
 
 
 def _chain_modules(enc):
@@ -931,23 +907,8 @@ def _chain_modules(enc):
 
 def _geometry_steps(enc, lvl):
     """Generator: one step per convolution of `_chain_modules`, issuing (wait=False) whatever that layer reads."""
-    cur = lvl
     for m in _chain_modules(enc):
-        v = _slab_variant_for(m, cur, m.in_channels, m.out_channels)
-        if m.subm:
-            if v is not None:
-                cur.subm_slab(ops.slab_block_rows(m.in_channels, v), wait=False)
-            else:
-                cur.subm_neighbors(m.kernel_size, wait=False)
-        else:
-            slots_meta = v is None and _gather_reads_slots(m, cur)
-            nxt, _ = cur.downsample(m.kernel_size, m.stride, m.padding, wait=False,
-                                    want_nbr=(v is None and not slots_meta) or LAYER_PROFILE is not None)
-            if v is not None:
-                cur.down_slab(m.kernel_size, m.stride, m.padding, ops.slab_block_rows(m.in_channels, v), wait=False)
-            elif slots_meta:
-                cur.down_slab(m.kernel_size, m.stride, m.padding, _GATHER_SLOT_ROWS, wait=False)
-            cur = nxt
+        lvl = lvl.forward_product(m, _route_for(m, lvl), wait=False)[0]
         yield m
 
 
@@ -961,12 +922,10 @@ class _Chain:
 
     Products are allocated under the geometry stream (its pool): a buffer of the main stream's pool may be a block a
     still-running convolution reads (see Level._fork), and once convolutions have been issued the chain can no longer rely on
-    the fork at the top of run_encoder for that.  They stay alive in their Level's caches until the join at the end of the pass."""
+    the fork at the top of the pass for that.  They stay alive in their Level's cache until the join at the end of the pass."""
 
     def __init__(self, enc, lvl, lookahead):
         mods = _chain_modules(enc)
-        self.strided = [not m.subm for m in mods]
-        self.main = torch.cuda.current_stream(lvl.device)
         self.pos = {id(m): i for i, m in enumerate(mods)}
         self.steps = _geometry_steps(enc, lvl)
         self.issued = 0
@@ -979,22 +938,10 @@ class _Chain:
         """Issue the products of modules [issued, upto]."""
         if self.issued > upto or self.issued >= self.total:
             return
-        _PREFETCHING[0] = True
-        try:
-            with torch.cuda.stream(self.gstream):
-                while self.issued <= upto and self.issued < self.total:
-                    if _CHAIN_HOLD and self.issued > 0 and self.strided[self.issued]:
-                        # The products of a strided layer (the next level's active set and everything built on it) start behind the
-                        # convolutions issued so far: they are not needed before the NEXT level's layers, and kept out from under
-                        # the layers they used to run beside — the strided layer of the level before (16 -> 32: 248 us beside the
-                        # level-3 set construction, 133 us alone); they land beside the first wide layers of the next level instead.
-                        ev = torch.cuda.Event()
-                        ev.record(self.main)
-                        self.gstream.wait_event(ev)
-                    next(self.steps)
-                    self.issued += 1
-        finally:
-            _PREFETCHING[0] = False
+        with _prefetching(), torch.cuda.stream(self.gstream):
+            while self.issued <= upto and self.issued < self.total:
+                next(self.steps)
+                self.issued += 1
 
     def before(self, conv):
         i = self.pos.get(id(conv))

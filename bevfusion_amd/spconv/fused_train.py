@@ -24,8 +24,6 @@ inference runs on:
 BatchNorm (+ ReLU, + identity) stays `spconv/bn.py`'s two-launch pair per direction.  16-bit compute only (autocast, or 16-bit
 weights); anything else — fp32 training, rows not promised to be in linear order, a module tree that is not conv -> BN1d [-> ReLU] /
 SparseBasicBlock — takes the module path."""
-import os
-
 import torch
 from torch import nn
 
@@ -33,7 +31,6 @@ from .. import _capi
 from . import bn as native_bn
 from . import fused, ops
 
-_ENABLED = os.environ.get("BEVAMD_SPCONV_FUSED_TRAIN", "1") != "0"
 _PAD_ROWS = 256     # feature buffers are allocated in whole 256-row blocks (the largest staged block), handed on as [:m] views
 
 
@@ -146,9 +143,7 @@ class _Plan:
         """Create the layers mods[len(layers) .. upto] and issue what their forward reads."""
         if len(self.layers) > upto:
             return
-        old = fused._PREFETCHING[0]
-        fused._PREFETCHING[0] = True
-        try:
+        with fused._prefetching():
             while len(self.layers) <= upto and len(self.layers) < len(self.mods):
                 m = self.mods[len(self.layers)]
                 if m.subm:
@@ -156,20 +151,17 @@ class _Plan:
                     L.issue()
                 else:
                     L = _Layer(m, self, self.cur, None)
-                    L.issue()
+                    nxt = _Lv(L.issue())
                     if L.wg_checked:
                         # in front of the read-back that carries its status word — on every pass, one that never runs a backward
                         # (a training-mode forward under no_grad) included: one slab_build launch on the geometry stream ahead of
                         # the step's sync, which before only issue_backward_products() made, behind the forward
                         L.issue(forward=False)
-                    nxt = _Lv(self.cur.level.downsample(m.kernel_size, m.stride, m.padding, wait=False, want_nbr=True)[0])
                     self.pending.append(nxt)
                     L.lv_out = nxt
                     self.cur = nxt
                 L.image, L.image_t = self.images.get(id(m), (None, None))
                 self.layers.append(L)
-        finally:
-            fused._PREFETCHING[0] = old
 
     def layer(self, conv):
         i = self.pos[id(conv)]
@@ -187,13 +179,10 @@ class _Plan:
         checked = [L for L in self.layers if L.wg_checked and L.wg_code]
         words = []
         for L in checked:
-            lvl, key = L.lv_in.level, (tuple(L.conv.kernel_size), tuple(L.conv.stride), tuple(L.conv.padding), L.wg_code, "table")
-            if key not in lvl._down_slab:
-                # only a caller that drives the layers by hand gets here (advance() has built the metadata inside its prefetch
-                # bracket): built on demand, OUTSIDE that bracket on purpose — Level._fork() then orders the geometry stream
-                # behind what the main stream has issued, as for every product asked for in the middle of a pass
-                L.issue(forward=False)
-            words.append(lvl._down_slab[key][0].status)
+            # advance() has built the metadata inside its prefetch bracket; only for a caller that drives the layers by hand is it
+            # built here, on demand and OUTSIDE that bracket on purpose — Level._fork() then orders the geometry stream behind
+            # what the main stream has issued, as for every product asked for in the middle of a pass
+            words.append(L.issue(forward=False).status)
         with self._on_geometry_stream():
             host = torch.cat([lv.level.n_dev.reshape(1) for lv in self.pending] + [w.reshape(1) for w in words]).cpu().tolist()
             for L, w, v in zip(checked, words, host[len(self.pending):]):
@@ -209,13 +198,9 @@ class _Plan:
         if self.late_issued:
             return
         self.late_issued = True
-        old = fused._PREFETCHING[0]
-        fused._PREFETCHING[0] = True
-        try:
+        with fused._prefetching():
             for L in self.layers:
                 L.issue(forward=False)
-        finally:
-            fused._PREFETCHING[0] = old
 
 
 class _Layer:
@@ -232,7 +217,9 @@ class _Layer:
         self.cin, self.cout = conv.in_channels, conv.out_channels
         self.K = conv.kernel_size[0] * conv.kernel_size[1] * conv.kernel_size[2]
         lvl = lv_in.level
-        self.variant = fused._slab_variant_for(conv, lvl, self.cin, self.cout) if conv.subm else None
+        # forward kernel and the product it reads; a strided layer keeps its int32 table (table_t) and runs on the gather kernels
+        self.route = fused._route_for(conv, lvl, gather=not conv.subm)
+        self.variant = self.route.variant if self.route.kernel == "slab" else None
         # staged-rows filter gradient: cin == cout layers as they are; the stem (cin 5 -> 16) with its rows zero-padded to cout
         # channels (round 6: its gather-kernel filter gradient took 172 + 49 us and wanted a hash index + an int32 table of level 1
         # that nothing else reads; padded to 16 -> 16 it is the 23-us kernel of the other level-1 layers, the extra rows of dW dropped)
@@ -245,8 +232,7 @@ class _Layer:
             if lib.bevamd_spconv_wgrad_slab_supported(ops._DT[plan.dtype], self.cout, self.cout) and ops.slab_grid_ok(lvl.shape, 128):
                 self.wg_code = int(lib.bevamd_spconv_wgrad_slab_block_rows(self.cout))
                 self.wg_cin = self.cout
-        elif (not conv.subm) and self.K == 27 and tuple(conv.kernel_size) == (3, 3, 3) and lvl.linear_order and lvl.allow_slab \
-                and os.environ.get("BEVAMD_SPCONV_WGRAD_SLAB_STRIDED", "1") != "0":
+        elif (not conv.subm) and self.K == 27 and tuple(conv.kernel_size) == (3, 3, 3) and lvl.linear_order and lvl.allow_slab:
             # the strided 3x3x3 layers (16 -> 32, 32 -> 64, 64 -> 128): the same kernel over metadata built from the layer's table
             # (taken only where a range cannot outgrow the metadata's 16-bit slots, or where the step checks it: strided_wgrad_route)
             lib = _capi.load()
@@ -262,23 +248,15 @@ class _Layer:
 
     # ---- products (built on the geometry stream by issue(); these calls find them cached and wait for their events) ----
     def issue(self, forward=True):
-        """forward=True: what the forward pass reads (and the level below needs); False: what only the backward pass reads."""
+        """forward=True: what the forward pass reads (and the level below needs), returns the output Level; False: what only the
+        backward pass reads, returns it (the filter gradient's metadata, or the table the gather kernel reads)."""
         conv, lvl = self.conv, self.lv_in.level
+        if forward:
+            return lvl.forward_product(conv, self.route, wait=False)[0]
         if conv.subm:
-            if forward:
-                if self.variant is not None:
-                    lvl.subm_slab(ops.slab_block_rows(self.cin, self.variant), wait=False)
-                else:
-                    lvl.subm_neighbors(conv.kernel_size, wait=False)
-            else:
-                if self.wg_code:
-                    lvl.subm_slab(self.wg_code, wait=False)
-                else:
-                    lvl.subm_neighbors(conv.kernel_size, wait=False)
-        elif forward:
-            lvl.downsample(conv.kernel_size, conv.stride, conv.padding, wait=False, want_nbr=True)
-        elif self.wg_code:
-            lvl.down_slab_from_table(conv.kernel_size, conv.stride, conv.padding, self.wg_code, wait=False)
+            return lvl.subm_slab(self.wg_code, wait=False) if self.wg_code else lvl.subm_neighbors(conv.kernel_size, wait=False)
+        if self.wg_code:
+            return lvl.down_slab_from_table(conv.kernel_size, conv.stride, conv.padding, self.wg_code, wait=False)
 
     def table(self):
         conv, lvl = self.conv, self.lv_in.level
@@ -333,22 +311,20 @@ class _LevelConv(torch.autograd.Function):
         image = L.image
         # the launch is bounded by the level's capacity and guarded by its device-side count, like the inference path; the buffer
         # holds the exact rows once they are known (a strided layer learns them right behind its own launch)
+        _, meta, nbr = lvl_in.forward_product(conv, L.route)
         if conv.subm:
             m = L.lv_out.n
             out = _rows_buffer(m, L.cout, plan.dtype, x.device)
-            if L.variant is not None:
-                meta = lvl_in.subm_slab(ops.slab_block_rows(L.cin, L.variant))
-                ops.sparse_conv_slab(x, image, meta, lvl_out.n_cap, L.cin, L.cout, num_out_dev=lvl_out.n_dev, out=out, variant=L.variant)
+            if meta is not None:
+                ops.sparse_conv_slab(x, image, meta, lvl_out.n_cap, L.cin, L.cout, num_out_dev=lvl_out.n_dev, out=out, variant=L.route.variant)
             else:
-                ops.sparse_conv_tiled(x, image, L.table(), lvl_out.n_cap, L.K, L.cin, L.cout, num_out_dev=lvl_out.n_dev, out=out,
-                                      variant=fused._variant_for(fused._frames_equivalent(lvl_in), L.K, L.cin, L.cout))
+                ops.sparse_conv_tiled(x, image, nbr, lvl_out.n_cap, L.K, L.cin, L.cout, num_out_dev=lvl_out.n_dev, out=out,
+                                      variant=L.route.variant)
         else:
-            nbr = L.table()
             plan.resolve()
             m = L.lv_out.n
             out = _rows_buffer(m, L.cout, plan.dtype, x.device)
-            ops.sparse_conv_tiled(x, image, nbr, m, L.K, L.cin, L.cout, out=out,
-                                  variant=fused._variant_for(fused._frames_equivalent(lvl_in), L.K, L.cin, L.cout))
+            ops.sparse_conv_tiled(x, image, nbr, m, L.K, L.cin, L.cout, out=out, variant=L.route.variant)
         ctx.L = L
         ctx.save_for_backward(x)
         return out
@@ -367,7 +343,7 @@ class _LevelConv(torch.autograd.Function):
         if ctx.needs_input_grad[0]:
             if conv.subm and L.variant is not None and L.cin == L.cout:
                 # the mirrored, transposed filter over the same metadata (module docstring)
-                meta = lvl_in.subm_slab(ops.slab_block_rows(L.cin, L.variant))
+                meta = lvl_in.subm_slab(L.route.block_rows)
                 dx = _rows_buffer(n_in, x.shape[1], plan.dtype, x.device)
                 ops.sparse_conv_slab(g, L.image_t, meta, lvl_in.n_cap, L.cout, L.cin, num_out_dev=lvl_in.n_dev, out=dx, variant=L.variant)
             else:
@@ -483,8 +459,6 @@ class _DenseBev(torch.autograd.Function):
 
 
 def unsupported_reason(enc, voxel_features, coors_order, num_voxels):
-    if not _ENABLED:
-        return "BEVAMD_SPCONV_FUSED_TRAIN=0"
     if not enc.training:
         return "module is in eval mode"
     if not voxel_features.is_cuda:
@@ -522,7 +496,6 @@ def run_encoder(enc, voxel_features, coors, batch_size, coors_order="linear"):
     if voxel_features.shape[1] != cin:
         raise fused.NotThisCall(f"voxel_features has {voxel_features.shape[1]} columns, the encoder reads {cin}")
     dev = voxel_features.device
-    coors = coors.int().contiguous()
     pitch = ops.padded_channels(cin)
     with torch.no_grad():
         if voxel_features.dtype == torch.float32 and voxel_features.is_contiguous() and not voxel_features.requires_grad:
@@ -535,28 +508,22 @@ def run_encoder(enc, voxel_features, coors, batch_size, coors_order="linear"):
             feats = None
     if feats is None:
         feats = torch.nn.functional.pad(voxel_features.to(dtype), (0, pitch - cin))
-    g = fused.geometry_stream(dev)
-    main = torch.cuda.current_stream(dev)
-    pool = fused._status_pool(dev)
-    if g is not None:
-        g.wait_stream(main)
-    lvl1 = fused.Level(coors, n, None, int(batch_size), enc.sparse_shape, gstream=g, linear_order=True, status_pool=pool)
-    lvl1.frames_hint = n / float(fused._ROWS_PER_FLAGSHIP_FRAME)
     mods = fused._chain_modules(enc)
-    plan = _Plan(enc, _Lv(lvl1, n), dtype, mods)
-    layers = True          # (the walkers' "this is not the validation walk" flag)
-    try:
+    with fused.open_pass(enc, coors, int(batch_size), linear_order=True, frames_hint=n / float(fused._ROWS_PER_FLAGSHIP_FRAME)) as lvl1:
+        plan = _Plan(enc, _Lv(lvl1, n), dtype, mods)
+        layers = True          # (the walkers' "this is not the validation walk" flag)
         strided = [i for i, m in enumerate(mods) if not m.subm]
         plan.advance((strided[0] if strided else len(mods)) - 1)          # level 1's forward products
         prepare_images(plan, dev, stem_needs_grad=voxel_features.requires_grad)
         # the device-side status words of the chain (fused._first_call_check), read BEFORE the feature pass on the first call of an
         # encoder (BEVAMD_SPCONV_CHECK=1: every call) — the kernels would stay inside their buffers either way, on a wrong rulebook.
-        # A checked pass builds everything first.
+        # A checked pass builds everything first.  Unlike the inference entries, which re-run on another route, a training step
+        # hands the call to the module path before any BatchNorm buffer is touched.
         if fused._CHECK or not enc.__dict__.get("_bevamd_train_geometry_checked"):
             plan.advance(len(mods) - 1)
             plan.issue_backward_products()
-            if g is not None:
-                g.synchronize()
+            if lvl1.gstream is not None:
+                lvl1.gstream.synchronize()
             bits = fused.geometry_status(lvl1)
             if bits:
                 raise fused.NotThisCall(f"geometry status {bits:#x} (1: a staged range overflowed its 16-bit slots, 2: rows promised as "
@@ -571,7 +538,4 @@ def run_encoder(enc, voxel_features, coors, batch_size, coors_order="linear"):
         x, lv = _sequential(enc.conv_out, x, lv, plan, layers)
         out = _DenseBev.apply(x, lv)
         plan.issue_backward_products()
-    finally:
-        if g is not None:
-            main.wait_stream(g)
     return out

@@ -223,7 +223,7 @@ def test_stem_layer_filter_gradient_on_the_staged_rows_kernel(dev, voxels):
     x = torch.nn.functional.pad(x5, (0, 3))
     y = fused_train._LevelConv.apply(x, conv.weight, L)
     y.backward(gy)
-    assert lvl.index is None and not lvl._subm                  # neither the hash index nor the int32 table exists
+    assert lvl.index is None and not lvl.has("subm_neighbors")                  # neither the hash index nor the int32 table exists
     # a caller that asks for the gradient of the voxel features (nobody in the reference does) gets it through the layer's table
     fused_train.prepare_images(plan, dev, stem_needs_grad=True)
     x5g = x5.clone().requires_grad_(True)

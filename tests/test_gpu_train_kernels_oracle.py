@@ -294,7 +294,7 @@ def test_stem_layer_vs_oracle(dev, ran, dtype, hint):
             assert tuple(dx.shape) == (c["n"], 5)
             results.append(_check(f"train {tag} dx", dx, c["dx_ref"], FWD_BAR[dtype]))
         else:
-            assert lvl.index is None and not lvl._subm          # neither the hash index nor the int32 table was built
+            assert lvl.index is None and not lvl.has("subm_neighbors")          # neither the hash index nor the int32 table was built
         assert all(ok for ok, _ in results), [msg for ok, msg in results if not ok]
     assert {r[3] for r in ran if r[0] == "slab"} == {fused._SLAB_NARROW_SUBM}
     _note(ran, hint)
