@@ -176,6 +176,11 @@ _EXT_SIGNATURES = {
     # head training targets
     "bevamd_centerhead_targets": (I, [P, P, P, I, I, I, I, P, I, I, P, P, I, I, ctypes.c_double, I, I, P, P, P, P, P, P]),
     "bevamd_heatmap_targets": (I, [P, P, P, I, I, I, I, I, P, P, I, I, ctypes.c_double, I, P, P, P]),
+    # TransFusion assignment: match costs, linear sum assignment, targets
+    "bevamd_match_costs": (I, [P, P, P, P, P, I, I, I, I, I, I, I, I, c_float, ctypes.c_double, ctypes.c_double, c_float, I, c_float, I,
+                               c_float, P, P, P, P, P, P]),
+    "bevamd_linear_sum_assignment": (I, [P, P, P, I, I, I, P, P, P]),
+    "bevamd_transfusion_assign_targets": (I, [P, P, P, P, P, P, P, I, I, I, I, I, I, I, I, LL, P, P, P, P, P, P, P, P, P, P]),
 }
 
 

@@ -59,6 +59,9 @@ NORM_LAYERS = Registry("norm layer")
 BACKBONES = Registry("backbone")
 VTRANSFORMS = Registry("vtransform")
 BBOX_CODERS = Registry("bbox coder")
+BBOX_ASSIGNERS = Registry("bbox assigner")
+MATCH_COST = Registry("match cost")
+IOU_CALCULATORS = Registry("iou calculator")
 
 for _name, _cls in (("BN", nn.BatchNorm2d), ("BN1d", nn.BatchNorm1d), ("BN2d", nn.BatchNorm2d),
                     ("BN3d", nn.BatchNorm3d), ("SyncBN", nn.SyncBatchNorm), ("GN", nn.GroupNorm), ("LN", nn.LayerNorm)):
@@ -99,7 +102,8 @@ def build_norm_layer(cfg, num_features, postfix=""):
 
 def register_everywhere(registry_name, cls, name=None):
     """Register in our registry and, if mmcv/mmdet/mmdet3d are importable, in theirs too."""
-    ours = {"conv": CONV_LAYERS, "backbone": BACKBONES, "vtransform": VTRANSFORMS, "bbox_coder": BBOX_CODERS}[registry_name]
+    ours = {"conv": CONV_LAYERS, "backbone": BACKBONES, "vtransform": VTRANSFORMS, "bbox_coder": BBOX_CODERS,
+            "bbox_assigner": BBOX_ASSIGNERS, "match_cost": MATCH_COST, "iou_calculator": IOU_CALCULATORS}[registry_name]
     ours.register_module(name=name, module=cls, force=True)
     try:  # pragma: no cover - mmcv is not installed in this image
         if registry_name == "conv":
@@ -108,6 +112,12 @@ def register_everywhere(registry_name, cls, name=None):
             from mmdet.models import BACKBONES as REAL
         elif registry_name == "bbox_coder":
             from mmdet.core.bbox.builder import BBOX_CODERS as REAL
+        elif registry_name == "bbox_assigner":
+            from mmdet.core.bbox.builder import BBOX_ASSIGNERS as REAL
+        elif registry_name == "match_cost":
+            from mmdet.core.bbox.match_costs.builder import MATCH_COST as REAL
+        elif registry_name == "iou_calculator":
+            from mmdet.core.bbox.iou_calculators.builder import IOU_CALCULATORS as REAL
         else:
             from mmdet3d.models.builder import VTRANSFORMS as REAL
         REAL.register_module(name=name, module=cls, force=True)

@@ -247,6 +247,68 @@ int bevamd_heatmap_targets(const float* boxes, const long long* labels, const in
                            int out_size_factor, int map_size, double gaussian_overlap, int min_radius, float* heatmap,
                            int* overflow, void* stream);
 
+
+/* The assignment end of TransFusionHead.get_targets (mmdet3d/models/heads/bbox/transfusion.py:357-524, 575 over
+ * core/bbox/assigners/hungarian_assigner.py:13-35, 82-142, BaseInstance3DBoxes.overlaps of core/bbox/structures/base_box3d.py:378-445
+ * and mmdet 2.x's FocalLossCost / ClassificationCost): match costs, a batched rectangular linear sum assignment, and the target
+ * rows that follow from it.  Nothing below synchronises the device, reads anything back or takes a workspace; every output
+ * element is written on every call; all of it can be captured in one graph.  LAUNCHES: bevamd_match_costs 2 (sizes, costs),
+ * bevamd_linear_sum_assignment 1, bevamd_transfusion_assign_targets 1.  Problem n = sample * layers + layer.
+ * Ground truth is packed as for the head targets above (boxes [num_rows, 7|9] fp32 LiDAR layout, labels [num_rows] int64,
+ * offsets [batch + 1] int32 ON THE DEVICE, the HOST bound max_boxes_per_sample 1 .. 1024; more: 4, unsupported, before any launch).
+ * STATUS bits (per problem): 1 a live cost entry is not finite; 2 a ground-truth label outside [0, classes); 4 the sample has more
+ *   boxes than the bound or its offsets name no range of the arrays (its live count is 0); 8 the solver's loop bound was reached or
+ *   a live size lies outside the buffer.
+ *
+ * bevamd_match_costs: boxes [batch, layers * num_proposals, box_dim] fp32 DECODED boxes (bevamd_transfusion_decode with
+ *   num_proposals = layers * K; NULL when neither box cost is asked for), logits [batch, classes, layers * num_proposals] fp32
+ *   (NULL with cls_mode 0).  cost, iou [batch, layers, num_proposals, max_boxes_per_sample] fp32: slot g of problem n is ground
+ *   truth offsets[sample] + g; slots past the live count are 0.  num_gt [batch * layers] int32: the live count (the `cols` of the
+ *   solver); status [batch * layers] int32.  cost = cls + reg + iou_cost, each term in the reference's fp32 operation order without
+ *   FMA contraction, sigmoid / log / pow / exp evaluated in double and rounded once:
+ *     cls_mode 1 FocalLossCost: p = sigmoid(logit[label]); neg = -log(1 - p + eps) * (1 - alpha) * p^gamma;
+ *       pos = -log(p + eps) * alpha * (1 - p)^gamma; (pos - neg) * cls_weight.  cls_mode 2 ClassificationCost:
+ *       -softmax(logits over classes)[label] * cls_weight.  A label outside [0, classes) makes the entry NaN and sets bits 1 and 2.
+ *     use_reg BBoxBEVL1Cost: (|dx| + |dy|) * reg_weight of (xy - pc_range[0:2]) / (pc_range[3:5] - pc_range[0:2]); pc_range: HOST,
+ *       6 floats (the fp32 values of the tensor the reference builds).
+ *     use_iou IoU3DCost: -iou * iou_weight; iou: BEV overlap of (x - dx / 2, y - dy / 2, x + dx / 2, y + dy / 2, yaw) in the
+ *       arithmetic of bevamd_iou3d_boxes_overlap_bev, times clamp(min(z + dz) - max(z), 0), over
+ *       clamp(v1 + v2 - overlap, 1e-8) with v = dx * dy * dz.  Without use_iou `iou` is 0.
+ * bevamd_linear_sum_assignment: scipy.optimize.linear_sum_assignment for num_problems problems over cost
+ *   [num_problems, max_rows, max_cols] fp32 with the live sizes rows / cols [num_problems] int32 READ FROM DEVICE MEMORY (NULL: the
+ *   full side), so that a graph replay may change them; entries outside the live block are never read.  max_rows, max_cols
+ *   1 .. 1024 (more: 4, unsupported, before any launch).  col4row [num_problems, max_rows] int32: the column of every live row, -1
+ *   for an unmatched row and for rows past the live count; min(rows, cols) rows are matched.  Shortest augmenting paths with dual
+ *   variables (Jonker-Volgenant / Crouse), over the smaller side, duals and path costs in fp64: optimal for the given fp32 matrix;
+ *   among equal path costs an unmatched column is preferred, then the lower one, so equal-cost optima may differ from scipy's.
+ *   One wave per problem; the cost block is staged in LDS when max_rows x max_cols x 4 bytes fit beside the state (12 x the
+ *   smaller + 28 x the larger side, in bytes) in 64 KiB, otherwise read through L2.  Every loop is bounded (an augmentation visits at most `cols` columns, there are
+ *   `rows` augmentations): a problem with a non-finite live entry (status 1), with a live size outside the buffer or over the loop
+ *   bound (status 8) returns all rows -1; other problems of the batch are not affected.  status [num_problems] int32.
+ * bevamd_transfusion_assign_targets: rows p = layer * num_proposals + k of every sample from col4row [batch * layers,
+ *   num_proposals] and iou (as above): labels [batch, P] int64 (num_classes, or the matched label), label_weights [batch, P] int64
+ *   (1, or pos_weight > 0 on positives), bbox_targets [batch, P, code_size] fp32 = TransFusionBBoxCoder.encode of the matched box
+ *   ((x - coder[0]) / coder[2], (y - coder[1]) / coder[3], z + dz * 0.5, log dims, sin, cos yaw (rounded once from double), vx, vy
+ *   with code_size 10, which needs 9 box columns; coder: HOST, 4 doubles {pc_range[0], pc_range[1], out_size_factor *
+ *   voxel_size[0], out_size_factor * voxel_size[1]}, each rounded to fp32 as the reference's scalar operands are), bbox_weights
+ *   (1 on positive rows), ious [batch, P] (the matched pair's iou clamped to [0, 1]), all zero on negative rows.  flags [batch]
+ *   int32: the OR of the sample's status words (status_cost may be NULL) and bit 4; a flagged sample is all negative (so is one
+ *   without ground truth, where the reference raises).  num_pos: one int32; matched_ious: one fp32, the mean over samples of
+ *   sum(ious[pos]) / max(n_pos, 1), summed in a fixed order. */
+int bevamd_match_costs(const float* boxes, const float* logits, const float* gt_boxes, const long long* gt_labels,
+                       const int* offsets, int num_rows, int box_dim, int batch, int layers, int num_proposals, int classes,
+                       int max_boxes_per_sample, int cls_mode, float cls_weight, double alpha, double gamma, float eps,
+                       int use_reg, float reg_weight, int use_iou, float iou_weight, const float* pc_range, float* cost,
+                       float* iou, int* num_gt, int* status, void* stream);
+int bevamd_linear_sum_assignment(const float* cost, const int* rows, const int* cols, int num_problems, int max_rows,
+                                 int max_cols, int* col4row, int* status, void* stream);
+int bevamd_transfusion_assign_targets(const int* col4row, const float* iou, const int* status_cost, const int* status_lsa,
+                                      const float* gt_boxes, const long long* gt_labels, const int* offsets, int num_rows,
+                                      int box_dim, int batch, int layers, int num_proposals, int max_boxes_per_sample,
+                                      int num_classes, int code_size, long long pos_weight, const double* coder,
+                                      long long* labels, long long* label_weights, float* bbox_targets, float* bbox_weights,
+                                      float* ious, int* flags, int* num_pos, float* matched_ious, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
