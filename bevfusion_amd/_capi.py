@@ -181,6 +181,8 @@ _EXT_SIGNATURES = {
                                c_float, P, P, P, P, P, P]),
     "bevamd_linear_sum_assignment": (I, [P, P, P, I, I, I, P, P, P]),
     "bevamd_transfusion_assign_targets": (I, [P, P, P, P, P, P, P, I, I, I, I, I, I, I, I, LL, P, P, P, P, P, P, P, P, P, P]),
+    # map segmentation metrics
+    "bevamd_seg_iou_counts": (I, [P, P, I, I, I, LL, P, I, P, P]),
 }
 
 

@@ -11,7 +11,8 @@ mmdet3d/core/bbox/coders/transfusion_bbox_coder.py, mmdet3d/core/post_processing
   * `CenterPointBBoxCoder`, `centerhead_get_bboxes`, `rotate_nms_segments`: the CenterHead end, re-exported from `centerhead`;
   * `centerhead_get_targets`, `transfusion_heatmap_targets`: the training targets of both heads, re-exported from `head_targets`;
   * `transfusion_get_targets`, `HungarianAssigner3D`, the match costs, `BboxOverlaps3D`, `linear_sum_assignment_batch`: the
-    assignment end of TransFusionHead.get_targets, re-exported from `head_assign`.
+    assignment end of TransFusionHead.get_targets, re-exported from `head_assign`;
+  * `seg_iou_counts`, `evaluate_map`: the map segmentation metrics of NuScenesDataset.evaluate_map, re-exported from `seg_head`.
 
 Dispatch: device tensors go through the library or raise (no torch formulation for them); host tensors run the reference's
 formulation written in torch / numpy with a STABLE descending argsort, which is the order the kernels are defined to produce
@@ -33,12 +34,13 @@ from .head_assign import (BBOX_ASSIGNERS, IOU_CALCULATORS, MATCH_COST, AssignRes
                           ClassificationCost, FocalLossCost, HungarianAssigner3D, IoU3DCost, linear_sum_assignment_batch,
                           transfusion_get_targets)                          # (the TransFusion assignment)
 from .registry import BBOX_CODERS, register_everywhere
+from .seg_head import evaluate_map, seg_iou_counts  # noqa: F401  (the map segmentation metrics)
 
 __all__ = ["circle_nms", "circle_nms_segments", "TransFusionBBoxCoder", "ProposalSelection", "transfusion_select_proposals",
            "transfusion_get_bboxes", "exempt_classes", "nms_tasks", "BBOX_CODERS", "CenterPointBBoxCoder", "centerhead_get_bboxes",
            "rotate_nms_segments", "centerhead_get_targets", "transfusion_heatmap_targets", "transfusion_get_targets",
            "linear_sum_assignment_batch", "HungarianAssigner3D", "AssignResult", "FocalLossCost", "ClassificationCost", "BBoxBEVL1Cost",
-           "IoU3DCost", "BboxOverlaps3D", "BBOX_ASSIGNERS", "MATCH_COST", "IOU_CALCULATORS"]
+           "IoU3DCost", "BboxOverlaps3D", "BBOX_ASSIGNERS", "MATCH_COST", "IOU_CALCULATORS", "seg_iou_counts", "evaluate_map"]
 
 MAX_PROPOSALS = 1024     # HE_MAX_K of the kernels: proposals per sample, rows per NMS segment
 _UNSUPPORTED = 4

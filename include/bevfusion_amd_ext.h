@@ -309,6 +309,17 @@ int bevamd_transfusion_assign_targets(const int* col4row, const float* iou, cons
                                       long long* labels, long long* label_weights, float* bbox_targets, float* bbox_weights,
                                       float* ious, int* flags, int* num_pos, float* matched_ious, void* stream);
 
+
+/* Map segmentation metrics.  Replace the counting of NuScenesDataset.evaluate_map (mmdet3d/datasets/nuscenes_dataset.py:498-530).
+ * bevamd_seg_iou_counts (2 launches: zero, count): pred [samples, classes, hw] fp32; label of the same shape, label_dtype 0 fp32
+ *   / 3 uint8 or bool, non-zero is true (as with .bool()); thresholds: DEVICE fp32 [num_thresholds], 1 .. 16.  counts [classes,
+ *   num_thresholds, 3] int64 = tp, fp, fn over samples and cells, the prediction being `pred >= threshold` in fp32 (a NaN is below
+ *   every threshold).  The call zeroes counts itself.  64-bit integer atomics: exact and independent of arrival order.  classes
+ *   1 .. 1024, samples * hw <= 2^36; code 1 for bad sizes, more than 16 thresholds or a null pointer, code 4 for another
+ *   label_dtype, both before any GPU work.  No synchronisation, no read-back, no workspace. */
+int bevamd_seg_iou_counts(const float* pred, const void* label, int label_dtype, int samples, int classes, long long hw,
+                          const float* thresholds, int num_thresholds, long long* counts, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
