@@ -183,6 +183,11 @@ _EXT_SIGNATURES = {
     "bevamd_transfusion_assign_targets": (I, [P, P, P, P, P, P, P, I, I, I, I, I, I, I, I, LL, P, P, P, P, P, P, P, P, P, P]),
     # map segmentation metrics
     "bevamd_seg_iou_counts": (I, [P, P, I, I, I, LL, P, I, P, P]),
+    # decoder layer attention
+    "bevamd_mha_workspace_bytes": (Z, [I, I, I, I]),
+    "bevamd_mha_plan": (I, [I, I, I, I, P]),
+    "bevamd_mha_forward": (I, [P, P, P, I, I, I, I, I, ctypes.c_double, ctypes.c_ulonglong, P, P, P, P, Z, P]),
+    "bevamd_mha_backward": (I, [P, P, P, P, P, P, I, I, I, I, ctypes.c_double, ctypes.c_ulonglong, P, P, P, P, Z, P]),
 }
 
 

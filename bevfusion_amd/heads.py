@@ -12,7 +12,9 @@ mmdet3d/core/bbox/coders/transfusion_bbox_coder.py, mmdet3d/core/post_processing
   * `centerhead_get_targets`, `transfusion_heatmap_targets`: the training targets of both heads, re-exported from `head_targets`;
   * `transfusion_get_targets`, `HungarianAssigner3D`, the match costs, `BboxOverlaps3D`, `linear_sum_assignment_batch`: the
     assignment end of TransFusionHead.get_targets, re-exported from `head_assign`;
-  * `seg_iou_counts`, `evaluate_map`: the map segmentation metrics of NuScenesDataset.evaluate_map, re-exported from `seg_head`.
+  * `seg_iou_counts`, `evaluate_map`: the map segmentation metrics of NuScenesDataset.evaluate_map, re-exported from `seg_head`;
+  * `TransformerDecoderLayer`, `MultiheadAttention`, `PositionEmbeddingLearned`, `fused_attention`: the head's learned stage, the
+    decoder layer over the fused attention kernels, re-exported from `decoder`.
 
 Dispatch: device tensors go through the library or raise (no torch formulation for them); host tensors run the reference's
 formulation written in torch / numpy with a STABLE descending argsort, which is the order the kernels are defined to produce
@@ -29,6 +31,7 @@ from torch.nn import functional as F
 
 from . import _capi
 from .centerhead import CenterPointBBoxCoder, centerhead_get_bboxes, rotate_nms_segments  # noqa: F401  (the CenterHead end)
+from .decoder import MultiheadAttention, PositionEmbeddingLearned, TransformerDecoderLayer, fused_attention  # noqa: F401  (the decoder layer)
 from .head_targets import centerhead_get_targets, transfusion_heatmap_targets  # noqa: F401  (the training targets)
 from .head_assign import (BBOX_ASSIGNERS, IOU_CALCULATORS, MATCH_COST, AssignResult, BBoxBEVL1Cost, BboxOverlaps3D,  # noqa: F401
                           ClassificationCost, FocalLossCost, HungarianAssigner3D, IoU3DCost, linear_sum_assignment_batch,
@@ -40,7 +43,8 @@ __all__ = ["circle_nms", "circle_nms_segments", "TransFusionBBoxCoder", "Proposa
            "transfusion_get_bboxes", "exempt_classes", "nms_tasks", "BBOX_CODERS", "CenterPointBBoxCoder", "centerhead_get_bboxes",
            "rotate_nms_segments", "centerhead_get_targets", "transfusion_heatmap_targets", "transfusion_get_targets",
            "linear_sum_assignment_batch", "HungarianAssigner3D", "AssignResult", "FocalLossCost", "ClassificationCost", "BBoxBEVL1Cost",
-           "IoU3DCost", "BboxOverlaps3D", "BBOX_ASSIGNERS", "MATCH_COST", "IOU_CALCULATORS", "seg_iou_counts", "evaluate_map"]
+           "IoU3DCost", "BboxOverlaps3D", "BBOX_ASSIGNERS", "MATCH_COST", "IOU_CALCULATORS", "seg_iou_counts", "evaluate_map",
+           "fused_attention", "MultiheadAttention", "PositionEmbeddingLearned", "TransformerDecoderLayer"]
 
 MAX_PROPOSALS = 1024     # HE_MAX_K of the kernels: proposals per sample, rows per NMS segment
 _UNSUPPORTED = 4

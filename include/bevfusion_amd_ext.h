@@ -320,6 +320,32 @@ int bevamd_transfusion_assign_targets(const int* col4row, const float* iou, cons
 int bevamd_seg_iou_counts(const float* pred, const void* label, int label_dtype, int samples, int classes, long long hw,
                           const float* thresholds, int num_thresholds, long long* counts, void* stream);
 
+/* Fused multi-head attention of the TransFusion decoder layer (mmdet3d/models/utils/transformer.py:244-493), head dimension 16:
+ * out = dropout(softmax(q k^T / 4)) v per head, the logits never stored.  q [B, L, H * 16], k, v [B, S, H * 16] contiguous and
+ * 16-byte aligned; out [B, L, H * 16] in the input dtype (0 fp32, 1 fp16); lse [B, H, L] fp32 = log sum exp of the scaled logits.
+ * The softmax and both accumulations are fp32 (v_mfma_f32_16x16x4_f32).  Shapes: 1 <= B <= 4095, 1 <= H <= 16, 1 <= L <= 1024,
+ * 1 <= S <= 2^20; anything else is code 1 before any GPU work (code 4 for another dtype, code 2 for a short workspace).
+ * bevamd_mha_workspace_bytes: host only; what forward and backward need (the larger); 0 for a shape the entry points reject.
+ * bevamd_mha_plan: host only; plan4 = {forward splits, keys per split (a multiple of 64), backward key blocks, keys per block (a
+ *   multiple of 256)}: functions of (B, H, L, S) alone, so equal calls are bit-equal and a captured graph replays.
+ * bevamd_mha_forward (2 launches): every split keeps a running (max, sum, out) per query; the second launch merges the splits in
+ *   order.  dropout_p in [0, 1): weight (b * H + h, query, key) is kept when a counter hash of (seed, b * H + h, query, key) reaches
+ *   dropout_p * 2^32, kept weights are scaled by 1 / (1 - p), the row sum uses the undropped weights.
+ *   stats (may be NULL): [2, B, H, L] fp32 = lse in two terms, the row maximum and the log of the row sum, which the backward reads
+ *   (their fp32 sum, lse, loses digits to a large maximum).
+ * bevamd_mha_backward (3 launches; fp32): delta = rowsum(dout * out); the weights are recomputed from stats, dS = P (dP - delta), with
+ *   the forward's mask from the same seed.  A workgroup owns a block of keys: dk, dv are written once; dq goes to one partial buffer
+ *   per key block that the last launch sums in block order.  No floating-point atomics.
+ * Both are asynchronous on `stream`: no synchronisation, no allocation, no read-back. */
+size_t bevamd_mha_workspace_bytes(int B, int H, int L, int S);
+int bevamd_mha_plan(int B, int H, int L, int S, int* plan4);
+int bevamd_mha_forward(const void* q, const void* k, const void* v, int B, int H, int L, int S, int dtype, double dropout_p,
+                       unsigned long long seed, void* out, float* lse, float* stats, void* workspace, size_t workspace_bytes,
+                       void* stream);
+int bevamd_mha_backward(const float* q, const float* k, const float* v, const float* out, const float* stats, const float* dout, int B,
+                        int H, int L, int S, double dropout_p, unsigned long long seed, float* dq, float* dk, float* dv,
+                        void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
