@@ -670,8 +670,10 @@ int bevamd_bev_pool_fused_columns_count(const uint32_t* cell_of_point, int n, in
   BEVAMD_REQUIRE((unsigned long long)b * d * h * w < 0xFFFFFFF0ull, "bev_pool_fused_columns_count: b*d*h*w too large");
   BEVAMD_REQUIRE(cell_of_point && keep && endm && run_first && total_runs, "bev_pool_fused_columns_count: null buffer");
   const int ncols = n / fh;
-  if (!ws || ws_bytes < scan_workspace_bytes((size_t)ncols)) {
-    set_error("bev_pool_fused_columns_count: workspace too small");
+  // the scan below needs less, but the contract is the published size: one number for callers and tests
+  const size_t need = bevamd_bev_pool_fused_columns_workspace_bytes(ncols, 0);
+  if (!ws || ws_bytes < need) {
+    set_error("bev_pool_fused_columns_count: workspace too small (%zu < %zu)", ws_bytes, need);
     return BEVAMD_ERR_WORKSPACE;
   }
   const uint32_t ncells = (uint32_t)((unsigned long long)b * d * h * w);

@@ -1378,15 +1378,18 @@ int bevamd_spconv_pairs_from_nbr(const int* nbr, int nbr_stride, int m, int kern
   hipStream_t stream = (hipStream_t)stream_;
   BEVAMD_REQUIRE(kernel_volume > 0 && m >= 0 && pairs_len >= 0, "spconv_pairs_from_nbr: bad sizes");
   BEVAMD_REQUIRE(indice_pairs && indice_num, "spconv_pairs_from_nbr: null output");
+  // every refusal comes before the first write: a refused call leaves the outputs alone
+  if (m > 0) {
+    BEVAMD_REQUIRE(nbr != nullptr, "spconv_pairs_from_nbr: nbr is null");
+    size_t need = bevamd_spconv_pairs_workspace_bytes(m, kernel_volume);
+    if (!ws || ws_bytes < need) {
+      set_error("spconv_pairs_from_nbr: workspace too small (%zu < %zu)", ws_bytes, need);
+      return BEVAMD_ERR_WORKSPACE;
+    }
+  }
   BEVAMD_HIP_CHECK(hipMemsetAsync(indice_pairs, 0xFF, (size_t)kernel_volume * 2 * pairs_len * sizeof(int), stream));
   BEVAMD_HIP_CHECK(hipMemsetAsync(indice_num, 0, (size_t)kernel_volume * sizeof(int), stream));
   if (m == 0) return BEVAMD_OK;
-  BEVAMD_REQUIRE(nbr != nullptr, "spconv_pairs_from_nbr: nbr is null");
-  size_t need = bevamd_spconv_pairs_workspace_bytes(m, kernel_volume);
-  if (!ws || ws_bytes < need) {
-    set_error("spconv_pairs_from_nbr: workspace too small (%zu < %zu)", ws_bytes, need);
-    return BEVAMD_ERR_WORKSPACE;
-  }
   Carver cv(ws, ws_bytes);
   const size_t e = (size_t)m * kernel_volume;
   uint32_t* flags = cv.take<uint32_t>(e);

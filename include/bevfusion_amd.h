@@ -160,6 +160,8 @@ int bevamd_bev_pool_fused_forward_scheduled(const float* depth, const void* ctx,
  *   _columns_build : slot_of_run [nruns] (position of a run in the stable (frame, cell) order; a run alone in its cell: 1 << 31 |
  *                    its row of out, stored by pass 1 directly — round 5), prow_start [b*d*h*w + 1]
  *                    (CSR over frame-major cells).  nruns = *total_runs read back once by the caller (plan time).
+ * ws: bevamd_bev_pool_fused_columns_workspace_bytes(cams*depth_bins*fw, 0) for _columns_count, (.., nruns) for _columns_build;
+ * both refuse a shorter one (code 2) before any launch.
  * Shapes: c % 4 == 0, fh <= 32, fw % 4 == 0 (bevamd_bev_pool_fused_columns_supported); plans with about as many runs as points
  * (a camera rolled by 90 degrees) should stay on the cell-centric kernels above. */
 int bevamd_bev_pool_fused_columns_supported(int c, int depth_bins, int fh, int fw);
@@ -479,7 +481,8 @@ int bevamd_spconv_dense_bev(const void* features, int elem_bytes, int pitch, int
 
 /* The reference's rulebook arrays (spconv_ops.h:56-59): indice_pairs [K, 2, pairs_len] int32 (-1
  * padded; [k][0] = input rows, [k][1] = output rows), indice_num [K].  Pairs of one offset are listed
- * by ascending output row (the reference's CUDA order is atomicAdd order, i.e. unspecified). */
+ * by ascending output row (the reference's CUDA order is atomicAdd order, i.e. unspecified).  Both arrays are fully written;
+ * a call refused for a short workspace (code 2) writes neither. */
 size_t bevamd_spconv_pairs_workspace_bytes(int m, int kernel_volume);
 int bevamd_spconv_pairs_from_nbr(const int* nbr, int nbr_stride, int m, int kernel_volume,
                                  int* indice_pairs, int pairs_len, int* indice_num, void* ws,
