@@ -14,7 +14,9 @@ mmdet3d/core/bbox/coders/transfusion_bbox_coder.py, mmdet3d/core/post_processing
     assignment end of TransFusionHead.get_targets, re-exported from `head_assign`;
   * `seg_iou_counts`, `evaluate_map`: the map segmentation metrics of NuScenesDataset.evaluate_map, re-exported from `seg_head`;
   * `TransformerDecoderLayer`, `MultiheadAttention`, `PositionEmbeddingLearned`, `fused_attention`: the head's learned stage, the
-    decoder layer over the fused attention kernels, re-exported from `decoder`.
+    decoder layer over the fused attention kernels, re-exported from `decoder`;
+  * `transfusion_loss`, `centerhead_loss`, `GaussianFocalLoss`, `FocalLoss`, `L1Loss`: the losses of both heads with their
+    gradients, re-exported from `head_losses`.
 
 Dispatch: device tensors go through the library or raise (no torch formulation for them); host tensors run the reference's
 formulation written in torch / numpy with a STABLE descending argsort, which is the order the kernels are defined to produce
@@ -36,6 +38,7 @@ from .head_targets import centerhead_get_targets, transfusion_heatmap_targets  #
 from .head_assign import (BBOX_ASSIGNERS, IOU_CALCULATORS, MATCH_COST, AssignResult, BBoxBEVL1Cost, BboxOverlaps3D,  # noqa: F401
                           ClassificationCost, FocalLossCost, HungarianAssigner3D, IoU3DCost, linear_sum_assignment_batch,
                           transfusion_get_targets)                          # (the TransFusion assignment)
+from .head_losses import LOSSES, FocalLoss, GaussianFocalLoss, L1Loss, centerhead_loss, transfusion_loss  # noqa: F401  (the losses)
 from .registry import BBOX_CODERS, register_everywhere
 from .seg_head import evaluate_map, seg_iou_counts  # noqa: F401  (the map segmentation metrics)
 
@@ -44,7 +47,8 @@ __all__ = ["circle_nms", "circle_nms_segments", "TransFusionBBoxCoder", "Proposa
            "rotate_nms_segments", "centerhead_get_targets", "transfusion_heatmap_targets", "transfusion_get_targets",
            "linear_sum_assignment_batch", "HungarianAssigner3D", "AssignResult", "FocalLossCost", "ClassificationCost", "BBoxBEVL1Cost",
            "IoU3DCost", "BboxOverlaps3D", "BBOX_ASSIGNERS", "MATCH_COST", "IOU_CALCULATORS", "seg_iou_counts", "evaluate_map",
-           "fused_attention", "MultiheadAttention", "PositionEmbeddingLearned", "TransformerDecoderLayer"]
+           "fused_attention", "MultiheadAttention", "PositionEmbeddingLearned", "TransformerDecoderLayer", "transfusion_loss",
+           "centerhead_loss", "GaussianFocalLoss", "FocalLoss", "L1Loss", "LOSSES"]
 
 MAX_PROPOSALS = 1024     # HE_MAX_K of the kernels: proposals per sample, rows per NMS segment
 _UNSUPPORTED = 4

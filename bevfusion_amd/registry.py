@@ -62,6 +62,7 @@ BBOX_CODERS = Registry("bbox coder")
 BBOX_ASSIGNERS = Registry("bbox assigner")
 MATCH_COST = Registry("match cost")
 IOU_CALCULATORS = Registry("iou calculator")
+LOSSES = Registry("loss")
 
 for _name, _cls in (("BN", nn.BatchNorm2d), ("BN1d", nn.BatchNorm1d), ("BN2d", nn.BatchNorm2d),
                     ("BN3d", nn.BatchNorm3d), ("SyncBN", nn.SyncBatchNorm), ("GN", nn.GroupNorm), ("LN", nn.LayerNorm)):
@@ -103,7 +104,7 @@ def build_norm_layer(cfg, num_features, postfix=""):
 def register_everywhere(registry_name, cls, name=None):
     """Register in our registry and, if mmcv/mmdet/mmdet3d are importable, in theirs too."""
     ours = {"conv": CONV_LAYERS, "backbone": BACKBONES, "vtransform": VTRANSFORMS, "bbox_coder": BBOX_CODERS,
-            "bbox_assigner": BBOX_ASSIGNERS, "match_cost": MATCH_COST, "iou_calculator": IOU_CALCULATORS}[registry_name]
+            "bbox_assigner": BBOX_ASSIGNERS, "match_cost": MATCH_COST, "iou_calculator": IOU_CALCULATORS, "loss": LOSSES}[registry_name]
     ours.register_module(name=name, module=cls, force=True)
     try:  # pragma: no cover - mmcv is not installed in this image
         if registry_name == "conv":
@@ -118,6 +119,8 @@ def register_everywhere(registry_name, cls, name=None):
             from mmdet.core.bbox.match_costs.builder import MATCH_COST as REAL
         elif registry_name == "iou_calculator":
             from mmdet.core.bbox.iou_calculators.builder import IOU_CALCULATORS as REAL
+        elif registry_name == "loss":
+            from mmdet.models.builder import LOSSES as REAL
         else:
             from mmdet3d.models.builder import VTRANSFORMS as REAL
         REAL.register_module(name=name, module=cls, force=True)

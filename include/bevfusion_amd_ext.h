@@ -346,6 +346,75 @@ int bevamd_mha_backward(const float* q, const float* k, const float* v, const fl
                         int H, int L, int S, double dropout_p, unsigned long long seed, float* dq, float* dk, float* dv,
                         void* workspace, size_t workspace_bytes, void* stream);
 
+/* Losses of the detection heads (csrc/ext/head_losses.hip).  Replace TransFusionHead.loss (mmdet3d/models/heads/bbox/
+ * transfusion.py:612-711), CenterHead.loss (centerpoint.py:597-633) and the mmdet 2.x losses they call: gaussian_focal_loss,
+ * py_sigmoid_focal_loss and l1_loss under weight_reduce_loss(reduction="mean", avg_factor).  All tensors fp32 and contiguous unless
+ * said otherwise.  Every cell term is evaluated in double from the fp32 inputs, summed in fp64 per workgroup and combined in a fixed
+ * order; the result is loss_weight * (fp32(sum) / avg) in fp32.  No floating-point atomics; every output element is written on
+ * every call; asynchronous on `stream`: no synchronisation, no allocation, no read-back, so all of it can be captured in a graph.
+ * Code 1 (bad sizes, a null pointer, more than 16 maps / tasks, a code of other than 8 / 10 columns) and code 4 (another dtype
+ * code, max_objs over 1024) are returned with an error string before any GPU work.
+ *
+ * bevamd_head_loss_plan: host only.  plan2 = {workgroups, cells per workgroup pass} for a map of `cells` cells (1 .. 2^40): the
+ *   workgroups are min(ceil(cells / pass), 1024); workgroup w owns the passes w, w + workgroups, ... of the map.
+ * bevamd_gaussian_focal_forward (2 launches: partials, finish): pred, target, cells: HOST arrays of num_maps (1 .. 16) device
+ *   pointers / cell counts; the bases need 4-byte alignment only (16-byte accesses of pred, and of grad where it shares pred's
+ *   alignment, run between a scalar head and tail; target is read wide where it is aligned at the same cells).  Per cell, p = clamp(sigmoid(x), 1e-4, 1 - 1e-4) with pred_is_logit 1 (clip_sigmoid), p =
+ *   x with 0; loss = -log(p + 1e-12) (1 - p)^alpha [t == 1] - log(1 - p + 1e-12) p^alpha (1 - t)^gamma.  num_pos [num_maps] fp32 =
+ *   the count of t == 1; loss [num_maps] = loss_weight * (sum / avg) with avg = *avg[t] when the HOST array avg and its entry t are
+ *   not NULL (a device scalar), else max(num_pos[t], 1).  partials: num_maps x W x 2 doubles, W = the plan's workgroups for the
+ *   LARGEST map of the call; every entry that is read is written first.
+ * bevamd_gaussian_focal_backward (1 launch): grad[t] (HOST array of device pointers, as pred) = d loss[t] / d pred[t] *
+ *   grad_out[t], in full: the per-cell derivative is recomputed from pred and target, is 0 where the clamp is active, is rounded once
+ *   to fp32 and multiplied by the fp32 grad_out[t] * loss_weight / avg; num_pos: the forward's output.
+ * bevamd_transfusion_layer_losses_forward (1 launch) / _backward (1 launch): the per-decoder-layer losses over P = L * K proposals,
+ *   layer l owning the proposals [l K, (l + 1) K).  Either half may be left out (scores NULL / center NULL), not both.
+ *   Class: scores [B, C, P] read in place; labels [B, P] int64, C = background (an all-zero one-hot row), a value outside [0, C] makes
+ *   the layer's loss and the row's gradients NaN; label_weights [B, P] fp32 (weight_dtype 0) or int64 (2).  loss_cls [L] = cls_weight
+ *   * sum(BCE_with_logits(x, y) (alpha y + (1 - alpha)(1 - y)) pt^gamma w) / avg, pt = (1 - s) y + s (1 - y), s = sigmoid(x).
+ *   Boxes: center [B, 2, P], height [B, 1, P], dim [B, 3, P], rot [B, 2, P], vel [B, 2, P] (NULL with D = 8, required with D = 10)
+ *   read in place as the columns 0-1, 2, 3-5, 6-7, 8-9 of the code; with height, dim, rot and vel all NULL `center` is instead one
+ *   packed [B, P, D] tensor, D 1 .. 16.  bbox_targets, bbox_weights [B, P, D]; code_weights: HOST, D floats (NULL: ones).  loss_box
+ *   [L] = box_weight * sum(|pred - target| fp32(bbox_weights * code_weights)) / avg.
+ *   avg = *avg_cls / *avg_box (device fp32 scalars) where given, else max(*num_pos, 1) with num_pos a device int32.
+ *   Backward: grad_cls, grad_box [L] device; grad_scores [B, C, P] and one gradient per piece (packed: grad_center alone), in full.
+ * bevamd_centerhead_box_loss_forward (1 launch) / _backward (2 launches: zero, scatter): maps: HOST array of 5 * num_tasks device
+ *   pointers, task-major {reg [B, 2, hw], height [B, 1, hw], dim [B, 3, hw], rot [B, 2, hw], vel [B, 2, hw]}, read only at the cells
+ *   ind[t] [B, max_objs] int64 (an index outside [0, hw) makes the task's loss NaN and gets no gradient); target[t] [B, max_objs,
+ *   10]; mask[t] [B, max_objs] uint8; num_tasks 1 .. 16, max_objs 1 .. 1024; code_weights: HOST, 10 floats.  weight = mask * (target
+ *   is not NaN) * code_weights; avg [num_tasks] = fp32(mask.sum()) + 1e-4 (an output, which the backward reads); loss [num_tasks] =
+ *   loss_weight * sum(|pred - target| weight) / avg.  A NaN target gives a NaN loss, as the reference's |pred - NaN| * 0 does.
+ *   Backward: the 5 * num_tasks gradient maps (grad_maps, laid out as maps) are zeroed inside the call; slots of a sample that share
+ *   a cell are summed in fp32 in slot order and written once by the first of them. */
+int bevamd_head_loss_plan(long long cells, int* plan2);
+int bevamd_gaussian_focal_forward(const float* const* pred, const float* const* target, const long long* cells, int num_maps,
+                                  int pred_is_logit, double alpha, double gamma, float loss_weight, const float* const* avg,
+                                  double* partials, float* loss, float* num_pos, void* stream);
+int bevamd_gaussian_focal_backward(const float* const* pred, const float* const* target, const long long* cells, int num_maps,
+                                   int pred_is_logit, double alpha, double gamma, float loss_weight, const float* const* avg,
+                                   const float* num_pos, const float* grad_out, float* const* grad, void* stream);
+int bevamd_transfusion_layer_losses_forward(const float* scores, const long long* labels, const void* label_weights, int weight_dtype,
+                                            const float* center, const float* height, const float* dim, const float* rot,
+                                            const float* vel, const float* bbox_targets, const float* bbox_weights,
+                                            const float* code_weights, const int* num_pos, const float* avg_cls, const float* avg_box,
+                                            int B, int C, int L, int K, int D, double alpha, double gamma, float cls_weight,
+                                            float box_weight, float* loss_cls, float* loss_box, void* stream);
+int bevamd_transfusion_layer_losses_backward(const float* scores, const long long* labels, const void* label_weights, int weight_dtype,
+                                             const float* center, const float* height, const float* dim, const float* rot,
+                                             const float* vel, const float* bbox_targets, const float* bbox_weights,
+                                             const float* code_weights, const int* num_pos, const float* avg_cls, const float* avg_box,
+                                             int B, int C, int L, int K, int D, double alpha, double gamma, float cls_weight,
+                                             float box_weight, const float* grad_cls, const float* grad_box, float* grad_scores,
+                                             float* grad_center, float* grad_height, float* grad_dim, float* grad_rot, float* grad_vel,
+                                             void* stream);
+int bevamd_centerhead_box_loss_forward(const float* const* maps, const long long* const* ind, const float* const* target,
+                                       const unsigned char* const* mask, int num_tasks, int batch, int max_objs, long long hw,
+                                       const float* code_weights, float loss_weight, float* loss, float* avg, void* stream);
+int bevamd_centerhead_box_loss_backward(const float* const* maps, const long long* const* ind, const float* const* target,
+                                        const unsigned char* const* mask, int num_tasks, int batch, int max_objs, long long hw,
+                                        const float* code_weights, float loss_weight, const float* avg, const float* grad_out,
+                                        float* const* grad_maps, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
