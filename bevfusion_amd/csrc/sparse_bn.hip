@@ -20,6 +20,17 @@ namespace bn {
 constexpr int THREADS = 256;
 constexpr int MAX_C = 256;
 
+// double -> float rounded to ODD (truncate, then set the last bit when inexact): rounding the result once more to a 16-bit type
+// gives the correctly rounded 16-bit value of the double — a plain (float)d first can land on a 16-bit tie the double was beside
+__device__ __forceinline__ float to_odd(double d) {
+  const float f = (float)d;
+  const double back = (double)f;
+  if (back == d) return f;
+  uint32_t u = __float_as_uint(f);
+  if (fabs(back) > fabs(d)) u -= 1u;   // rounded away from zero: one step back (never across zero: |f| > |d| > 0)
+  return __uint_as_float(u | 1u);      // NaN stays NaN
+}
+
 template <int DT> struct Row;          // DT 0: fp32 (4 channels per 16-byte vector), 1: fp16, 2: bf16 (8 per vector)
 template <> struct Row<0> {
   static constexpr int VEC = 4;
@@ -206,6 +217,23 @@ __device__ __forceinline__ void slab_sums(long long n, int C, float* sa, float* 
   __syncthreads();
 }
 
+// per-channel pivot of the shifted sums, channel group `cv` (VEC channels): the median of rows 0, n / 2 and n - 1
+template <int DT>
+__device__ __forceinline__ void pivot(const char* __restrict__ x, long long n, long long stride, int cv, float (&x0)[Row<DT>::VEC]) {
+  typedef Row<DT> R;
+  typedef typename R::V V;
+  const size_t esz = DT == 0 ? 4 : 2;
+  const V v0 = *(const V*)(x + (size_t)cv * R::VEC * esz);
+  const V v1 = *(const V*)(x + ((size_t)(n / 2) * stride + (size_t)cv * R::VEC) * esz);
+  const V v2 = *(const V*)(x + ((size_t)(n - 1) * stride + (size_t)cv * R::VEC) * esz);
+  float a[R::VEC], b[R::VEC], c[R::VEC];
+  R::unpack(v0, a);
+  R::unpack(v1, b);
+  R::unpack(v2, c);
+#pragma unroll
+  for (int j = 0; j < R::VEC; ++j) x0[j] = fmaxf(fminf(a[j], b[j]), fminf(fmaxf(a[j], b[j]), c[j]));
+}
+
 template <int DT, int U>
 __global__ __launch_bounds__(THREADS) void bn_stats_kernel(const void* __restrict__ x_, long long n, int C, long long stride,
                                                            float eps, float momentum, float* __restrict__ mean,
@@ -217,13 +245,15 @@ __global__ __launch_bounds__(THREADS) void bn_stats_kernel(const void* __restric
   __shared__ float sa[MAX_C], sb[MAX_C];
   const char* x = (const char*)x_;
   const size_t esz = DT == 0 ? 4 : 2;
-  // SHIFTED sums: p = sum (x - x0), q = sum (x - x0)^2 with x0 = row 0 of the tensor — the same pivot in every
-  // workgroup, a value of the channel's own distribution — so that var = q/n - (p/n)^2 does not cancel when |mean| >> std
-  // (E[x^2] - mean^2 on raw fp32 sums loses ~1e-7 * mean^2 / var of relative accuracy; torch's batch_norm runs Welford).
+  // SHIFTED sums: p = sum (x - x0), q = sum (x - x0)^2 with one pivot x0 per channel — the same in every workgroup,
+  // a value of the channel's own distribution — so that var = q/n - (p/n)^2 does not cancel when |mean| >> std (E[x^2] - mean^2
+  // on raw fp32 sums loses ~1e-7 * mean^2 / var of relative accuracy; torch's batch_norm runs Welford).  x0 = the median of rows
+  // 0, n / 2 and n - 1: no single row decides it (with row 0 alone as the pivot, a first row 50 sigma out cost 8e-5 of invstd).
+  // Two more lines that every wave of every workgroup reads: +0.3 us per launch (tools/time_bn.py, 20 layers: 0.42 -> 0.42 .. 0.43 ms).
   slab_sums<R::VEC, U>(n, C, sa, sb, [&](long long r, long long step, long long hi, int cv, float (&p)[R::VEC], float (&q)[R::VEC]) {
     V v[U];
     float x0[R::VEC];
-    R::unpack(*(const V*)(x + (size_t)cv * R::VEC * esz), x0);
+    pivot<DT>(x, n, stride, cv, x0);   // every trip, as row 0 was: its three loads go out with the trip's own (cache hits after the first)
 #pragma unroll
     for (int u = 0; u < U; ++u) {
       const long long ru = r + u * step < hi ? r + u * step : r;
@@ -241,11 +271,11 @@ __global__ __launch_bounds__(THREADS) void bn_stats_kernel(const void* __restric
   });
   finish_totals(sa, sb, C, part, gpart, ticket, [&](int c, double s, double ss) {
     float x0v[R::VEC];
-    R::unpack(*(const V*)(x + (size_t)(c / R::VEC) * R::VEC * esz), x0v);
+    pivot<DT>(x, n, stride, c / R::VEC, x0v);                // the pivot of the slabs, recomputed from the same three rows
     const double ms = s / (double)n;                         // mean of the shifted values
     const double m = (double)x0v[c % R::VEC] + ms;
     double var = ss / (double)n - ms * ms;
-    var = var > 0.0 ? var : 0.0;
+    var = var < 0.0 ? 0.0 : var;                             // a NaN stays one (torch: NaN invstd and running_var)
     mean[c] = (float)m;
     invstd[c] = (float)(1.0 / sqrt(var + (double)eps));
     if (running_mean) running_mean[c] = (float)((1.0 - (double)momentum) * (double)running_mean[c] + (double)momentum * m);
@@ -258,7 +288,11 @@ __global__ __launch_bounds__(THREADS) void bn_stats_kernel(const void* __restric
 
 // Elementwise kernels: lanes-per-row (C / VEC) divides THREADS, so a thread keeps ONE channel group for all its rows — its
 // per-channel constants load once — and walks rows `rows_per_trip` apart, four trips' loads issued together.
-template <int DT>
+// EXACT (16-bit rows with a residual): t1 = (x - mean) * (invstd * w) + b is evaluated in fp64 and rounded ONCE
+// to the storage type: in fp32, 7e-5 of the t1 lie so close to a 16-bit tie that they fall on its other side (torch's as well); alone
+// that is one ulp, but where t1 + residual is a tie too, round-half-even sends the two sums to even neighbours TWO ulps apart (one
+// element of y in a million).  Without a residual the fp32 evaluation stays: the fp64 one takes 22 % longer (four level shapes, fp16: 90 -> 110 us).
+template <int DT, bool EXACT>
 __global__ __launch_bounds__(THREADS) void bn_apply_kernel(const void* __restrict__ x_, long long n, int C, long long stride,
                                                            const float* __restrict__ mean, const float* __restrict__ invstd,
                                                            const float* __restrict__ weight, const float* __restrict__ bias,
@@ -280,26 +314,34 @@ __global__ __launch_bounds__(THREADS) void bn_apply_kernel(const void* __restric
   float mu[R::VEC];
 #pragma unroll
   for (int j = 0; j < R::VEC; ++j) mu[j] = mean[c0 + j];
+  double scd[EXACT ? R::VEC : 1], cd[EXACT ? R::VEC : 1];                             // EXACT: t1 = x * scd + cd
+  if (EXACT) {
+#pragma unroll
+    for (int j = 0; j < R::VEC; ++j) {
+      scd[j] = (double)invstd[c0 + j] * (double)(weight ? weight[c0 + j] : 1.f);      // exact: two fp32 factors
+      cd[j] = fma(-(double)mu[j], scd[j], (double)sh[j]);
+    }
+  }
   for (long long r0 = (long long)blockIdx.x * (THREADS / lpr) + (int)threadIdx.x / lpr; r0 < n; r0 += 4 * step) {
     V vx[4], vr[4];
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
       const long long r = r0 + u * step < n ? r0 + u * step : r0;
       vx[u] = *(const V*)((const char*)x_ + ((size_t)r * stride + c0) * esz);
-      if (res_) vr[u] = *(const V*)((const char*)res_ + ((size_t)r * res_stride + c0) * esz);
+      if (EXACT || res_) vr[u] = *(const V*)((const char*)res_ + ((size_t)r * res_stride + c0) * esz);
     }
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
       if (r0 + u * step >= n) break;
       float f[R::VEC], g[R::VEC];
       R::unpack(vx[u], f);
-      if (res_) R::unpack(vr[u], g);
+      if (EXACT || res_) R::unpack(vr[u], g);
 #pragma unroll
       for (int j = 0; j < R::VEC; ++j) {
         // torch's transform_input: (x - mean) * (invstd * w) + b in fp32, rounded to the storage type; the add and the ReLU of the
         // block are separate 16-bit tensors in the unfused pipeline, so each rounds once
-        float v = R::round((f[j] - mu[j]) * sc[j] + sh[j]);
-        if (res_) v = R::round(v + g[j]);
+        float v = EXACT ? R::round(to_odd(fma((double)f[j], scd[j], cd[j]))) : R::round((f[j] - mu[j]) * sc[j] + sh[j]);
+        if (EXACT || res_) v = R::round(v + g[j]);
         if (relu) v = v > 0.f ? v : (v != v ? v : 0.f);
         f[j] = v;
       }
@@ -495,7 +537,8 @@ int bevamd_sparse_bn_stats(const void* x, int dtype, long long n, int c, long lo
 }
 
 /* y = BatchNorm(x) with the given statistics [+ residual] [ReLU], rounded to the storage type after each of the three steps (the
- * unfused pipeline's tensors).  weight / bias / residual optional (NULL). */
+ * unfused pipeline's tensors).  weight / bias / residual optional (NULL).  16-bit rows with a residual: the normalised value is the
+ * correctly rounded one (fp64 inside), see bn_apply_kernel. */
 int bevamd_sparse_bn_apply(const void* x, int dtype, long long n, int c, long long stride, const float* mean, const float* invstd,
                            const float* weight, const float* bias, const void* residual, long long res_stride, int relu, void* y,
                            long long y_stride, void* stream_) {
@@ -506,7 +549,11 @@ int bevamd_sparse_bn_apply(const void* x, int dtype, long long n, int c, long lo
   BEVAMD_REQUIRE(x && y && mean && invstd && stride >= c && y_stride >= c && (!residual || res_stride >= c),
                  "sparse_bn_apply: null buffer / bad pitch");
   const unsigned g = apply_grid(n, c, dtype);
-#define BEVAMD_GO(DT) bn_apply_kernel<DT><<<dim3(g), dim3(THREADS), 0, stream>>>(x, n, c, stride, mean, invstd, weight, bias, residual, res_stride, relu, y, y_stride)
+#define BEVAMD_GO(DT)                                                                                                                          \
+  do {                                                                                                                                         \
+    if (residual && DT != 0) bn_apply_kernel<DT, true><<<dim3(g), dim3(THREADS), 0, stream>>>(x, n, c, stride, mean, invstd, weight, bias, residual, res_stride, relu, y, y_stride); \
+    else bn_apply_kernel<DT, false><<<dim3(g), dim3(THREADS), 0, stream>>>(x, n, c, stride, mean, invstd, weight, bias, residual, res_stride, relu, y, y_stride); \
+  } while (0)
   if (dtype == 0) BEVAMD_GO(0); else if (dtype == 1) BEVAMD_GO(1); else BEVAMD_GO(2);
 #undef BEVAMD_GO
   BEVAMD_LAUNCH_CHECK("bn_apply");

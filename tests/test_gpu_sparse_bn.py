@@ -143,7 +143,7 @@ def test_sparse_encoder_training_step_native_vs_torch_batchnorm(dev):
 
 def test_statistics_of_channels_with_a_large_mean(dev):
     """|mean| >> std.  E[x^2] - mean^2 on raw fp32 sums cancels (relative error ~1e-7 * mean^2 / var: at mean 300,
-    std 0.05 that is the whole variance); the kernels accumulate sums shifted by the tensor's first row, like a Welford pass starts."""
+    std 0.05 that is the whole variance); the kernels accumulate sums shifted by a value of the channel's own (the median of three rows), like a Welford pass starts."""
     n, c = 50000, 32
     g = torch.Generator(device=dev).manual_seed(3)
     mean = torch.linspace(-300.0, 300.0, c, device=dev)
