@@ -168,6 +168,9 @@ _EXT_SIGNATURES = {
     "bevamd_head_gather_queries": (I, [P, I, I, I, I, I, ctypes.c_ulonglong, P, I, P, I, I, P, I, P, P, P, P]),
     "bevamd_transfusion_decode": (I, [P, P, P, P, P, P, P, P, I, I, I, I, P, P, c_float, I, P, P, P, P, P]),
     "bevamd_circle_nms": (I, [P, P, I, P, I, P, I, I, P, P, P, P, P]),
+    # TransFusion head: category encoding and the fused prediction heads
+    "bevamd_head_class_encoding": (I, [P, P, P, P, I, I, I, I, P]),
+    "bevamd_head_ffn_forward": (I, [P, I, I, I, I, I, P, P, P, P, P, P, P, I, P, I, I, P]),
     # CenterHead ends
     "bevamd_centerpoint_select_workspace_bytes": (Z, [I, I, I, I]),
     "bevamd_centerpoint_select": (I, [P, P, I, I, I, I, I, I, P, P, P, Z, P]),

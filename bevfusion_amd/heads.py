@@ -16,7 +16,9 @@ mmdet3d/core/bbox/coders/transfusion_bbox_coder.py, mmdet3d/core/post_processing
   * `TransformerDecoderLayer`, `MultiheadAttention`, `PositionEmbeddingLearned`, `fused_attention`: the head's learned stage, the
     decoder layer over the fused attention kernels, re-exported from `decoder`;
   * `transfusion_loss`, `centerhead_loss`, `GaussianFocalLoss`, `FocalLoss`, `L1Loss`: the losses of both heads with their
-    gradients, re-exported from `head_losses`.
+    gradients, re-exported from `head_losses`;
+  * `TransFusionHead`, `FFN`, `ConvModule`, `head_class_encoding`, `head_ffn_forward`: the head as a module, its category encoding
+    and its prediction heads fused for eval mode, re-exported from `transfusion_head`.
 
 Dispatch: device tensors go through the library or raise (no torch formulation for them); host tensors run the reference's
 formulation written in torch / numpy with a STABLE descending argsort, which is the order the kernels are defined to produce
@@ -41,6 +43,7 @@ from .head_assign import (BBOX_ASSIGNERS, IOU_CALCULATORS, MATCH_COST, AssignRes
 from .head_losses import LOSSES, FocalLoss, GaussianFocalLoss, L1Loss, centerhead_loss, transfusion_loss  # noqa: F401  (the losses)
 from .registry import BBOX_CODERS, register_everywhere
 from .seg_head import evaluate_map, seg_iou_counts  # noqa: F401  (the map segmentation metrics)
+from .transfusion_head import HEADS, FFN, ConvModule, TransFusionHead, head_class_encoding, head_ffn_forward  # noqa: F401  (the module)
 
 __all__ = ["circle_nms", "circle_nms_segments", "TransFusionBBoxCoder", "ProposalSelection", "transfusion_select_proposals",
            "transfusion_get_bboxes", "exempt_classes", "nms_tasks", "BBOX_CODERS", "CenterPointBBoxCoder", "centerhead_get_bboxes",
@@ -48,7 +51,8 @@ __all__ = ["circle_nms", "circle_nms_segments", "TransFusionBBoxCoder", "Proposa
            "linear_sum_assignment_batch", "HungarianAssigner3D", "AssignResult", "FocalLossCost", "ClassificationCost", "BBoxBEVL1Cost",
            "IoU3DCost", "BboxOverlaps3D", "BBOX_ASSIGNERS", "MATCH_COST", "IOU_CALCULATORS", "seg_iou_counts", "evaluate_map",
            "fused_attention", "MultiheadAttention", "PositionEmbeddingLearned", "TransformerDecoderLayer", "transfusion_loss",
-           "centerhead_loss", "GaussianFocalLoss", "FocalLoss", "L1Loss", "LOSSES"]
+           "centerhead_loss", "GaussianFocalLoss", "FocalLoss", "L1Loss", "LOSSES", "TransFusionHead", "FFN", "ConvModule",
+           "head_class_encoding", "head_ffn_forward", "HEADS"]
 
 MAX_PROPOSALS = 1024     # HE_MAX_K of the kernels: proposals per sample, rows per NMS segment
 _UNSUPPORTED = 4

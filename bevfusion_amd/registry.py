@@ -1,5 +1,5 @@
 """Minimal stand-in for the mmcv/mmdet registries the reference registers its ops in
-(mmcv.cnn.CONV_LAYERS, mmcv.cnn NORM_LAYERS, mmdet BACKBONES, mmdet3d VTRANSFORMS — models/builder.py:5-41).
+(mmcv.cnn.CONV_LAYERS, mmcv.cnn NORM_LAYERS, mmdet BACKBONES, mmdet3d VTRANSFORMS and HEADS — models/builder.py:5-41).
 
 mmcv / mmdet are not vendored in the reference tree and are not installed here.  When they ARE importable the
 classes below are ALSO registered in the real registries, so reference configs (`type: SparseEncoder`,
@@ -63,6 +63,7 @@ BBOX_ASSIGNERS = Registry("bbox assigner")
 MATCH_COST = Registry("match cost")
 IOU_CALCULATORS = Registry("iou calculator")
 LOSSES = Registry("loss")
+HEADS = Registry("head")
 
 for _name, _cls in (("BN", nn.BatchNorm2d), ("BN1d", nn.BatchNorm1d), ("BN2d", nn.BatchNorm2d),
                     ("BN3d", nn.BatchNorm3d), ("SyncBN", nn.SyncBatchNorm), ("GN", nn.GroupNorm), ("LN", nn.LayerNorm)):
@@ -104,7 +105,7 @@ def build_norm_layer(cfg, num_features, postfix=""):
 def register_everywhere(registry_name, cls, name=None):
     """Register in our registry and, if mmcv/mmdet/mmdet3d are importable, in theirs too."""
     ours = {"conv": CONV_LAYERS, "backbone": BACKBONES, "vtransform": VTRANSFORMS, "bbox_coder": BBOX_CODERS,
-            "bbox_assigner": BBOX_ASSIGNERS, "match_cost": MATCH_COST, "iou_calculator": IOU_CALCULATORS, "loss": LOSSES}[registry_name]
+            "bbox_assigner": BBOX_ASSIGNERS, "match_cost": MATCH_COST, "iou_calculator": IOU_CALCULATORS, "loss": LOSSES, "head": HEADS}[registry_name]
     ours.register_module(name=name, module=cls, force=True)
     try:  # pragma: no cover - mmcv is not installed in this image
         if registry_name == "conv":
@@ -121,6 +122,8 @@ def register_everywhere(registry_name, cls, name=None):
             from mmdet.core.bbox.iou_calculators.builder import IOU_CALCULATORS as REAL
         elif registry_name == "loss":
             from mmdet.models.builder import LOSSES as REAL
+        elif registry_name == "head":
+            from mmdet3d.models.builder import HEADS as REAL
         else:
             from mmdet3d.models.builder import VTRANSFORMS as REAL
         REAL.register_module(name=name, module=cls, force=True)

@@ -158,6 +158,39 @@ int bevamd_circle_nms(const float* xy, const float* score, int num_rows, const i
                       unsigned char* keep, long long* keep_order, int* seg_counts, void* stream);
 
 
+/* The learned ends of TransFusionHead.forward_single around the decoder layer (mmdet3d/models/heads/bbox/transfusion.py:283-288
+ * and :311-312, FFN of mmdet3d/models/utils/transformer.py:496-575).  One launch each, no workspace, no device synchronisation,
+ * no float atomics: equal calls give bit-equal results and both can be captured in a graph.
+ *
+ * bevamd_head_class_encoding: query_feat [batch, channels, num_queries] fp32, IN PLACE:
+ *   query_feat[b, c, k] += weight[c, labels[b, k]] + bias[c], with labels [batch, num_queries] int64, weight
+ *   [channels, num_classes] (the Conv1d weight [channels, num_classes, 1]) and bias [channels] fp32.  The sum in parentheses is
+ *   rounded first, as the reference's convolution over the one-hot rounds it (its other products are exact zeros); no FMA
+ *   contraction: the result is bit-equal to the reference's fp32 arithmetic.  A label outside [0, num_classes) — where
+ *   F.one_hot raises — adds NOTHING to that query (not the bias either), reads nothing outside weight and raises no fault.
+ *   Exactly batch * channels * num_queries floats of query_feat are read and written, batch * num_queries labels read.
+ * bevamd_head_ffn_forward: every prediction head of one decoder layer in eval mode.  x [batch, in_channels, num_queries] fp32.
+ *   head_channels / w1 / scales / shifts / w2 / biases / outs are HOST arrays of num_heads entries; per head h the DEVICE
+ *   pointers w1[h] [head_conv, in_channels] (the first Conv1d, no bias), scales[h] / shifts[h] [head_conv] (BatchNorm1d folded:
+ *   scale = weight / sqrt(running_var + eps), shift = bias - running_mean * scale), w2[h] [head_channels[h], head_conv] and
+ *   biases[h] [head_channels[h]] (the second Conv1d), all fp32, w1[h] and w2[h] 16-byte aligned:
+ *     out_h[b, c, col_offset + p] = biases[h][c] + sum_j w2[h][c, j] * relu(scales[h][j] * sum_k w1[h][j, k] * x[b, k, p] + shifts[h][j])
+ *   with outs[h] laid out [batch, head_channels[h], out_stride]: exactly the columns [col_offset, col_offset + num_queries) of
+ *   every row are written and nothing else, so layer l of an auxiliary head writes with col_offset = l * num_queries into the
+ *   [batch, c, layers * num_queries] tensor the reference builds with torch.cat.  query_pos: optional [batch, num_queries, 2]
+ *   fp32; with it, head center_head (2 channels; negative: none) gets + query_pos[b, p, c] after its bias, the reference's
+ *   res_layer["center"] + query_pos.permute(0, 2, 1).  fp32 FMA with fp32 accumulation in ascending k and j; the hidden
+ *   activations stay in LDS.  Limits, checked on the host before any GPU work, anything else returns 4 (unsupported):
+ *   in_channels a multiple of 4 up to 256, head_conv a multiple of 16 up to 128, head_channels 1 .. 32, 1 .. 8 heads,
+ *   num_queries >= 1, 0 <= col_offset and col_offset + num_queries <= out_stride.  batch 0 .. 65535 (0: nothing to do). */
+int bevamd_head_class_encoding(float* query_feat, const long long* labels, const float* weight, const float* bias, int batch,
+                               int channels, int num_queries, int num_classes, void* stream);
+int bevamd_head_ffn_forward(const float* x, int batch, int in_channels, int num_queries, int head_conv, int num_heads,
+                            const int* head_channels, const void* const* w1, const void* const* scales,
+                            const void* const* shifts, const void* const* w2, const void* const* biases, const float* query_pos,
+                            int center_head, void* const* outs, int out_stride, int col_offset, void* stream);
+
+
 /* The non-learned end of CenterHead (mmdet3d/models/heads/bbox/centerpoint.py:637-884 get_bboxes / get_task_detections and
  * CenterPointBBoxCoder.decode, core/bbox/coders/centerpoint_bbox_coders.py:62-225).  Nothing below synchronises the device or
  * reads anything back; every call is a fixed number of launches on `stream` for ANY number of tasks and samples and can be
