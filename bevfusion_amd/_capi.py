@@ -171,6 +171,8 @@ _EXT_SIGNATURES = {
     # TransFusion head: category encoding and the fused prediction heads
     "bevamd_head_class_encoding": (I, [P, P, P, P, I, I, I, I, P]),
     "bevamd_head_ffn_forward": (I, [P, I, I, I, I, I, P, P, P, P, P, P, P, I, P, I, I, P]),
+    # CenterHead: the fused task heads
+    "bevamd_center_heads_forward": (I, [P, I, I, I, I, I, I, I, P, P, P, LL, P, LL, P]),
     # CenterHead ends
     "bevamd_centerpoint_select_workspace_bytes": (Z, [I, I, I, I]),
     "bevamd_centerpoint_select": (I, [P, P, I, I, I, I, I, I, P, P, P, Z, P]),

@@ -18,7 +18,9 @@ mmdet3d/core/bbox/coders/transfusion_bbox_coder.py, mmdet3d/core/post_processing
   * `transfusion_loss`, `centerhead_loss`, `GaussianFocalLoss`, `FocalLoss`, `L1Loss`: the losses of both heads with their
     gradients, re-exported from `head_losses`;
   * `TransFusionHead`, `FFN`, `ConvModule`, `head_class_encoding`, `head_ffn_forward`: the head as a module, its category encoding
-    and its prediction heads fused for eval mode, re-exported from `transfusion_head`.
+    and its prediction heads fused for eval mode, re-exported from `transfusion_head`;
+  * `CenterHead`, `SeparateHead`, `center_heads_forward`: the other detection head as a module and its task heads fused for eval
+    mode, re-exported from `centerhead_module`.
 
 Dispatch: device tensors go through the library or raise (no torch formulation for them); host tensors run the reference's
 formulation written in torch / numpy with a STABLE descending argsort, which is the order the kernels are defined to produce
@@ -43,6 +45,8 @@ from .head_assign import (BBOX_ASSIGNERS, IOU_CALCULATORS, MATCH_COST, AssignRes
 from .head_losses import LOSSES, FocalLoss, GaussianFocalLoss, L1Loss, centerhead_loss, transfusion_loss  # noqa: F401  (the losses)
 from .registry import BBOX_CODERS, register_everywhere
 from .seg_head import evaluate_map, seg_iou_counts  # noqa: F401  (the map segmentation metrics)
+from .centerhead_module import (CenterHead, FoldedCenterHeads, SeparateHead, center_heads_forward,  # noqa: F401  (the CenterHead module)
+                                center_heads_pack_w1, center_heads_unpack_w1, fold_center_heads)
 from .transfusion_head import HEADS, FFN, ConvModule, TransFusionHead, head_class_encoding, head_ffn_forward  # noqa: F401  (the module)
 
 __all__ = ["circle_nms", "circle_nms_segments", "TransFusionBBoxCoder", "ProposalSelection", "transfusion_select_proposals",
@@ -52,7 +56,8 @@ __all__ = ["circle_nms", "circle_nms_segments", "TransFusionBBoxCoder", "Proposa
            "IoU3DCost", "BboxOverlaps3D", "BBOX_ASSIGNERS", "MATCH_COST", "IOU_CALCULATORS", "seg_iou_counts", "evaluate_map",
            "fused_attention", "MultiheadAttention", "PositionEmbeddingLearned", "TransformerDecoderLayer", "transfusion_loss",
            "centerhead_loss", "GaussianFocalLoss", "FocalLoss", "L1Loss", "LOSSES", "TransFusionHead", "FFN", "ConvModule",
-           "head_class_encoding", "head_ffn_forward", "HEADS"]
+           "head_class_encoding", "head_ffn_forward", "HEADS", "CenterHead", "SeparateHead", "FoldedCenterHeads", "center_heads_forward",
+           "center_heads_pack_w1", "center_heads_unpack_w1", "fold_center_heads"]
 
 MAX_PROPOSALS = 1024     # HE_MAX_K of the kernels: proposals per sample, rows per NMS segment
 _UNSUPPORTED = 4

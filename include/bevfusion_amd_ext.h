@@ -191,6 +191,34 @@ int bevamd_head_ffn_forward(const float* x, int batch, int in_channels, int num_
                             int center_head, void* const* outs, int out_stride, int col_offset, void* stream);
 
 
+/* The task heads of CenterHead.forward_single in eval mode (mmdet3d/models/heads/bbox/centerpoint.py:121-125 and :351-352): for
+ * every head of every task Conv2d(64 -> 64, k x k, padding k / 2, no bias) -> BatchNorm2d (folded) -> ReLU -> Conv2d(64 -> c, k x k,
+ * padding k / 2, bias) on the shared map, ONE launch, no workspace, no device synchronisation, no atomics: equal calls give
+ * bit-equal results, a sample's result does not depend on the batch, and the call can be captured in a graph.
+ *
+ * bevamd_center_heads_forward: x [batch, channels, height, width] fp32, contiguous.  heads_per_task [num_tasks] and head_channels
+ *   [sum of heads_per_task] are HOST arrays (heads in task order).  packed: ONE DEVICE buffer, 16-byte aligned, of exactly
+ *   packed_floats floats holding per head, heads in order, with k2 = final_kernel^2:
+ *     w1 in fragment order, 4096 k2 floats: element [m][s4][lane][q] (m < 2, s4 < 8 k2, lane < 64, q < 4) is
+ *       weight1[m * 32 + (lane & 31)][ci][tap / final_kernel][tap % final_kernel] with 2 * (4 * s4 + q) + (lane >> 5) = tap * 64 + ci;
+ *     scale [64], shift [64]: scale = bn.weight / sqrt(running_var + eps), shift = bn.bias - running_mean * scale;
+ *     w2 [c][tap][64] = weight2[c][j][tap / final_kernel][tap % final_kernel]; bias [c], padded with zeros to a multiple of 4.
+ *   out: ONE buffer of exactly out_floats = batch * sum(c) * height * width floats in which head i owns the contiguous block
+ *   [batch, c_i, height, width] after the blocks of the heads before it.  Every element of out is written, nothing else is, and x
+ *   is only read.
+ *     hidden_h[b, j, y, x] = relu(scale_h[j] * sum_{tap, ci} weight1_h[j, ci, tap] * x[b, ci, (y, x) + tap] + shift_h[j])
+ *     out_h[b, c, y, x]    = bias_h[c] + sum_{tap, j} weight2_h[c, j, tap] * hidden_h[b, j, (y, x) + tap]
+ *   with x and hidden taken as zero outside the map.  The first sum is four v_mfma_f32_32x32x2_f32 chains in ascending (tap, ci),
+ *   chain q taking the channel pairs with (ci / 2) mod 4 = q, added as (s0 + s1) + (s2 + s3); the second is four fp32 fmaf chains in
+ *   ascending (tap, j), chain q taking j mod 4 = q, added the same way; the hidden activations stay in LDS.
+ *   Limits, checked on the host before any GPU work, anything else returns 4 (unsupported): channels = head_conv = 64,
+ *   final_kernel 1 or 3, 1 .. 8 tasks of 1 .. 8 heads, 1 .. 16 channels per head.  height, width >= 1; batch 0 .. 65535 (0:
+ *   nothing to do).  Code 1: a null pointer, bad sizes, packed_floats or out_floats that do not fit the heads. */
+int bevamd_center_heads_forward(const float* x, int batch, int channels, int head_conv, int height, int width, int final_kernel,
+                                int num_tasks, const int* heads_per_task, const int* head_channels, const float* packed,
+                                long long packed_floats, float* out, long long out_floats, void* stream);
+
+
 /* The non-learned end of CenterHead (mmdet3d/models/heads/bbox/centerpoint.py:637-884 get_bboxes / get_task_detections and
  * CenterPointBBoxCoder.decode, core/bbox/coders/centerpoint_bbox_coders.py:62-225).  Nothing below synchronises the device or
  * reads anything back; every call is a fixed number of launches on `stream` for ANY number of tasks and samples and can be
