@@ -173,6 +173,7 @@ _EXT_SIGNATURES = {
     "bevamd_head_ffn_forward": (I, [P, I, I, I, I, I, P, P, P, P, P, P, P, I, P, I, I, P]),
     # CenterHead: the fused task heads
     "bevamd_center_heads_forward": (I, [P, I, I, I, I, I, I, I, P, P, P, LL, P, LL, P]),
+    "bevamd_bev_conv_forward": (I, [P, I, P, I, I, I, I, I, I, I, I, I, I, P, LL, P, P, P, I, I, I, LL, P]),
     # CenterHead ends
     "bevamd_centerpoint_select_workspace_bytes": (Z, [I, I, I, I]),
     "bevamd_centerpoint_select": (I, [P, P, I, I, I, I, I, I, P, P, P, Z, P]),

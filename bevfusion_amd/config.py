@@ -102,7 +102,7 @@ def build_hot_path(cfg):
     """Instantiate the hot-path modules a BEVFusion config names: the camera view transform, the LiDAR voxelizer + backbone
     (sparse encoder or pillar encoder) and the radar voxelizer + backbone (fusion_models/bevfusion.py:36-69).  Returns a
     dict with whatever is present."""
-    from . import pillar_encoder, sparse_encoder, vtransforms  # noqa: F401  (registration side effects)
+    from . import bev_trunk, pillar_encoder, sparse_encoder, vtransforms  # noqa: F401  (registration side effects)
     from .registry import BACKBONES, VTRANSFORMS
     from .voxel import Voxelization
 

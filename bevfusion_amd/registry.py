@@ -64,6 +64,8 @@ MATCH_COST = Registry("match cost")
 IOU_CALCULATORS = Registry("iou calculator")
 LOSSES = Registry("loss")
 HEADS = Registry("head")
+FUSERS = Registry("fuser")
+NECKS = Registry("neck")
 
 for _name, _cls in (("BN", nn.BatchNorm2d), ("BN1d", nn.BatchNorm1d), ("BN2d", nn.BatchNorm2d),
                     ("BN3d", nn.BatchNorm3d), ("SyncBN", nn.SyncBatchNorm), ("GN", nn.GroupNorm), ("LN", nn.LayerNorm)):
@@ -102,10 +104,25 @@ def build_norm_layer(cfg, num_features, postfix=""):
     return _ABBR.get(typ, "norm") + str(postfix), layer
 
 
+def build_upsample_layer(cfg, *args, **kwargs):
+    """The part of mmcv.cnn.build_upsample_layer the reference's configs use: `deconv` -> nn.ConvTranspose2d(*args, **kwargs, **cfg);
+    `nearest` / `bilinear` -> nn.Upsample with mode = type."""
+    if not isinstance(cfg, dict) or "type" not in cfg:
+        raise TypeError(f"cfg must be a dict with a 'type' key, got {cfg!r}")
+    cfg = dict(cfg)
+    typ = cfg.pop("type")
+    if typ == "deconv":
+        return nn.ConvTranspose2d(*args, **kwargs, **cfg)
+    if typ in ("nearest", "bilinear"):
+        return nn.Upsample(*args, mode=typ, **kwargs, **cfg)
+    raise KeyError(f"Unrecognized upsample type {typ}")
+
+
 def register_everywhere(registry_name, cls, name=None):
     """Register in our registry and, if mmcv/mmdet/mmdet3d are importable, in theirs too."""
     ours = {"conv": CONV_LAYERS, "backbone": BACKBONES, "vtransform": VTRANSFORMS, "bbox_coder": BBOX_CODERS,
-            "bbox_assigner": BBOX_ASSIGNERS, "match_cost": MATCH_COST, "iou_calculator": IOU_CALCULATORS, "loss": LOSSES, "head": HEADS}[registry_name]
+            "bbox_assigner": BBOX_ASSIGNERS, "match_cost": MATCH_COST, "iou_calculator": IOU_CALCULATORS, "loss": LOSSES, "head": HEADS,
+            "fuser": FUSERS, "neck": NECKS}[registry_name]
     ours.register_module(name=name, module=cls, force=True)
     try:  # pragma: no cover - mmcv is not installed in this image
         if registry_name == "conv":
@@ -124,6 +141,10 @@ def register_everywhere(registry_name, cls, name=None):
             from mmdet.models.builder import LOSSES as REAL
         elif registry_name == "head":
             from mmdet3d.models.builder import HEADS as REAL
+        elif registry_name == "fuser":
+            from mmdet3d.models.builder import FUSERS as REAL
+        elif registry_name == "neck":
+            from mmdet.models import NECKS as REAL
         else:
             from mmdet3d.models.builder import VTRANSFORMS as REAL
         REAL.register_module(name=name, module=cls, force=True)

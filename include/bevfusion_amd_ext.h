@@ -219,6 +219,40 @@ int bevamd_center_heads_forward(const float* x, int batch, int channels, int hea
                                 long long packed_floats, float* out, long long out_floats, void* stream);
 
 
+/* One layer of the dense BEV trunk in eval mode (mmdet3d/models/fusers/conv.py ConvFuser, models/backbones/second.py SECOND,
+ * models/necks/second.py SECONDFPN): convolution + folded BatchNorm + ReLU in ONE launch on 16-bit storage (dtype 0: fp16, 1: bf16)
+ * with fp32 accumulation on v_mfma_f32_16x16x32; no workspace, no device synchronisation, no atomics, no split-K: equal calls give
+ * bit-equal results, a sample's result does not depend on the batch, and the call can be captured in a graph.
+ *
+ * bevamd_bev_conv_forward: the input is the channel concatenation of src0 (channels0) and, when channels1 > 0, src1 (channels1),
+ *   both [batch, c, height, width] in src_layout (0: NCHW, 1: NHWC = [batch, height, width, c]), contiguous; an NHWC source is
+ *   16-byte aligned.  Modes: mode 0 kernel 3 stride 1 or 2 (padding 1, output (H + 2 - 3) / stride + 1), mode 0 kernel 1 stride 1,
+ *   mode 1 kernel 2 stride 2 (ConvTranspose2d, output 2H x 2W).  With Cin = channels0 + channels1, nch = ceil(Cin / 32),
+ *   taps = kernel^2 for mode 0 and 1 for mode 1, groups = 1 for mode 0 and 4 for mode 1, packed holds exactly
+ *   packed_elems = groups * out_channels * nch * taps * 32 16-bit elements, 16-byte aligned, in A-fragment order:
+ *     element [g][mt][chunk][tap][lane][j] (mt < out_channels / 16, lane < 64, j < 8) is
+ *     w[co = 16 mt + (lane & 15)][ci = 32 chunk + 8 (lane >> 4) + j] of tap (ky, kx) = (tap / kernel, tap % kernel) for mode 0
+ *     (w = Conv2d.weight[co][ci][ky][kx]) and of tap (dy, dx) = (g / 2, g % 2) for mode 1 (w = ConvTranspose2d.weight[ci][co][dy][dx]),
+ *     zero where ci >= Cin.
+ *   scale, shift: [out_channels] fp32, 16-byte aligned (scale = bn.weight / sqrt(running_var + eps), shift = bn.bias -
+ *   running_mean * scale; never folded into the 16-bit weights).
+ *     y[b, co, p] = round16(max(fma(sum_{chunk, tap, ci} w * x, scale[co], shift[co]), 0))
+ *   with x zero outside the map, ONE fp32 accumulator chain per element in ascending (chunk, tap, ci).  y is written into the
+ *   channels [dst_channel_offset, dst_channel_offset + out_channels) of dst [batch, dst_channels_total, OH, OW] in dst_layout
+ *   (dst_elems = batch * dst_channels_total * OH * OW elements); exactly that window is written, nothing else, and the sources
+ *   are only read inside their extents.  Limits, checked on the host before any GPU work, anything else returns 4 (unsupported):
+ *   the three modes above, channels0 a multiple of 16 (>= 16), channels1 0 or a multiple of 16, out_channels a multiple of 32, an
+ *   NHWC destination with dst_channels_total and dst_channel_offset in multiples of 4.  height, width >= 1; batch 0 .. 65535 (0:
+ *   nothing to do).  Code 1: a null or misaligned pointer, bad sizes, packed_elems or dst_elems that do not fit the layer.
+ *   The entry takes no extents of the sources, of scale and of shift and cannot tell a host pointer from a device pointer: the
+ *   caller guarantees device buffers of batch * channels * height * width elements per source and out_channels floats each for
+ *   scale and shift (the Python wrapper checks both and refuses host tensors). */
+int bevamd_bev_conv_forward(const void* src0, int channels0, const void* src1, int channels1, int src_layout, int dtype, int batch,
+                            int height, int width, int out_channels, int kernel, int stride, int mode, const void* packed,
+                            long long packed_elems, const float* scale, const float* shift, void* dst, int dst_channels_total,
+                            int dst_channel_offset, int dst_layout, long long dst_elems, void* stream);
+
+
 /* The non-learned end of CenterHead (mmdet3d/models/heads/bbox/centerpoint.py:637-884 get_bboxes / get_task_detections and
  * CenterPointBBoxCoder.decode, core/bbox/coders/centerpoint_bbox_coders.py:62-225).  Nothing below synchronises the device or
  * reads anything back; every call is a fixed number of launches on `stream` for ANY number of tasks and samples and can be
