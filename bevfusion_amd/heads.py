@@ -22,7 +22,9 @@ mmdet3d/core/bbox/coders/transfusion_bbox_coder.py, mmdet3d/core/post_processing
   * `CenterHead`, `SeparateHead`, `center_heads_forward`: the other detection head as a module and its task heads fused for eval
     mode, re-exported from `centerhead_module`;
   * `ConvFuser`, `SECOND`, `SECONDFPN`, `bev_conv_forward`, `fold_bev_layer`: the dense BEV trunk in front of the heads as modules
-    and its fused convolution + BatchNorm + ReLU layer for eval mode, re-exported from `bev_trunk`.
+    and its fused convolution + BatchNorm + ReLU layer for eval mode, re-exported from `bev_trunk`;
+  * `fold_conv_bias_bn`, `fold_depth_stem`, `fold_depth_head`, `depth_stem_forward`, `depth_head_forward`: the learned nets of the
+    camera view transforms on 16-bit operands, re-exported from `cam_nets`.
 
 Dispatch: device tensors go through the library or raise (no torch formulation for them); host tensors run the reference's
 formulation written in torch / numpy with a STABLE descending argsort, which is the order the kernels are defined to produce
@@ -40,6 +42,8 @@ from torch.nn import functional as F
 from . import _capi
 from .bev_trunk import (SECOND, SECONDFPN, ConvFuser, FoldedBevLayer, bev_conv_forward, bev_pack_weight,  # noqa: F401  (the BEV trunk)
                         bev_unpack_weight, fold_bev_layer)
+from .cam_nets import (DepthHeadFold, DepthStemFold, depth_head_forward, depth_stem_forward, fold_conv_bias_bn,  # noqa: F401
+                       fold_depth_head, fold_depth_stem)                    # (the camera depth nets)
 from .centerhead import CenterPointBBoxCoder, centerhead_get_bboxes, rotate_nms_segments  # noqa: F401  (the CenterHead end)
 from .decoder import MultiheadAttention, PositionEmbeddingLearned, TransformerDecoderLayer, fused_attention  # noqa: F401  (the decoder layer)
 from .head_targets import centerhead_get_targets, transfusion_heatmap_targets  # noqa: F401  (the training targets)
@@ -62,7 +66,8 @@ __all__ = ["circle_nms", "circle_nms_segments", "TransFusionBBoxCoder", "Proposa
            "centerhead_loss", "GaussianFocalLoss", "FocalLoss", "L1Loss", "LOSSES", "TransFusionHead", "FFN", "ConvModule",
            "head_class_encoding", "head_ffn_forward", "HEADS", "CenterHead", "SeparateHead", "FoldedCenterHeads", "center_heads_forward",
            "center_heads_pack_w1", "center_heads_unpack_w1", "fold_center_heads", "ConvFuser", "SECOND", "SECONDFPN", "FoldedBevLayer",
-           "bev_conv_forward", "bev_pack_weight", "bev_unpack_weight", "fold_bev_layer"]
+           "bev_conv_forward", "bev_pack_weight", "bev_unpack_weight", "fold_bev_layer", "DepthStemFold", "DepthHeadFold",
+           "fold_conv_bias_bn", "fold_depth_stem", "fold_depth_head", "depth_stem_forward", "depth_head_forward"]
 
 MAX_PROPOSALS = 1024     # HE_MAX_K of the kernels: proposals per sample, rows per NMS segment
 _UNSUPPORTED = 4

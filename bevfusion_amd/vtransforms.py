@@ -12,6 +12,9 @@ What changed underneath (`BaseTransform.bev_pool`, base.py:141-176):
   * the reduction reads the feature rows through the sort permutation (no `feats[indices]` copy) and writes
     every BEV cell once; the result is returned as a channels-last VIEW of that buffer ([B, C*D, H, W] values
     identical to the reference's `torch.cat(x.unbind(dim=2), 1)`).
+The learned nets of `get_cam_feats` (`dtransform`, `depthnet`) are the reference's fp32 torch layers by default; with
+`cam_nets_dtype = torch.float16 | torch.bfloat16` they run, in eval mode on the GPU, through the fused 16-bit kernels of
+`cam_nets.py`, which hand depth and context to `bev_pool` in the layouts its fused kernel reads.
 Reference defects handled as SURVEY.md lists them: D2 (`get_cam_feats` arity) and D3 (DepthLSSTransform gets
 scalar 1-channel depth, no height expansion — the semantics the released checkpoint's `Conv2d(1, 8, 1)` needs).
 """
@@ -22,8 +25,9 @@ from typing import Tuple
 import torch
 from torch import nn
 
-from . import _capi
+from . import _capi, cam_nets
 from .bev_pool import BevPoolPlan, bev_pool
+from .bev_trunk import _no_grad_needed, bev_conv_forward
 from .registry import register_everywhere
 
 __all__ = ["BaseTransform", "BaseDepthTransform", "LSSTransform", "DepthLSSTransform", "gen_dx_bx"]
@@ -100,6 +104,46 @@ class BaseTransform(nn.Module):
         # 3x3 inverses of the calibration on the device path: False = bevamd_lss_camera_matrices / bevamd_mat3_inverse
         # (fp64 adjugate, no LAPACK call, no host sync); True = torch.inverse like the reference, call for call
         self.lapack_inverse = False
+        # the learned nets of get_cam_feats (dtransform, depthnet): None = the fp32 torch layers, as the reference's @force_fp32;
+        # torch.float16 / torch.bfloat16 = the user opts into 16-bit operands with fp32 accumulation through the fused kernels
+        # (cam_nets.py) in eval mode on the GPU; see cam_nets_fusable
+        self.cam_nets_dtype = None
+
+    def cam_nets_fusable(self, x, d=None):
+        """True when get_cam_feats(x[, d]) takes the fused 16-bit route.  All or nothing: a transform without learned nets of the
+        served structure, `cam_nets_dtype` None, train mode, host tensors or a gradient keep the fp32 torch layers."""
+        if self.cam_nets_dtype not in (torch.float16, torch.bfloat16) or self.training:
+            return False
+        if not (torch.is_tensor(x) and x.is_cuda and x.dim() == 5 and x.is_floating_point() and x.shape[2] == self.in_channels
+                and x.shape[0] * x.shape[1] >= 1 and x.shape[3] >= 1 and x.shape[4] >= 1):
+            return False
+        if not self.cam_nets_served() or not self._cam_nets_inputs(x, d):
+            return False
+        if any(p.device != x.device for p in self.depthnet.parameters()):
+            return False
+        return _no_grad_needed(self, [t for t in (x, d) if torch.is_tensor(t)])
+
+    def cam_nets_served(self):
+        """True when the learned nets have exactly the structure and the channel counts the fused kernels serve, whatever the
+        tensors: eval-mode BatchNorms with running statistics, `in_channels` a multiple of 32 up to 512, D 1 .. 128, C a multiple of
+        4 up to 128.  A transform without such nets: False."""
+        return False
+
+    def _cam_nets_inputs(self, x, d):
+        """What the transform asks of the inputs beyond [B, N, in_channels, fH, fW] features on the GPU."""
+        return True
+
+    def _head_served(self, conv):
+        return cam_nets.head_served(self.in_channels, self.D, self.C) and cam_nets._plain_conv(conv) \
+            and (conv.kernel_size, conv.stride, conv.padding) == ((1, 1), (1, 1), (0, 0)) \
+            and (conv.in_channels, conv.out_channels) == (self.in_channels, self.D + self.C)
+
+    def _cam_feats_result(self, depth, ctx, B, N):
+        """depth [B * N, D, fH, fW] and ctx [B * N, fH, fW, C] of the head kernel -> what get_cam_feats returns: `ctx` as a
+        [B, N, C, fH, fW] VIEW of the NHWC buffer, so that bev_pool's permute(...).contiguous() copies nothing."""
+        _, D, fH, fW = depth.shape
+        fact = FactoredCamFeats(depth.view(B, N, D, fH, fW), ctx.view(B, N, fH, fW, self.C).permute(0, 1, 4, 2, 3))
+        return fact if self.fused_cam_feats else fact.materialize()
 
     def create_frustum(self):
         """base.py:66-89."""
@@ -534,7 +578,22 @@ class LSSTransform(BaseTransform):
         self.depthnet = nn.Conv2d(in_channels, self.D + self.C, 1)
         self.downsample = _downsample_block(out_channels, downsample)
 
+    def cam_nets_served(self):
+        return self._head_served(self.depthnet)
+
+    def _cam_feats_fused(self, x):
+        """The cast to channels-last 16-bit (one torch launch), then the head kernel; None where the entry point refuses."""
+        B, N, C, fH, fW = x.shape
+        dtype = self.cam_nets_dtype
+        xh = x.detach().reshape(B * N, C, fH, fW).to(dtype=dtype, memory_format=torch.channels_last)
+        res = cam_nets.depth_head_forward(xh, cam_nets.fold_depth_head(self.depthnet, self.D, self.C, dtype))
+        return None if res is None else self._cam_feats_result(res[0], res[1], B, N)
+
     def get_cam_feats(self, x, *args):
+        if self.cam_nets_fusable(x):
+            res = self._cam_feats_fused(x)
+            if res is not None:
+                return res
         (x,) = _fp32(x)
         B, N, C, fH, fW = x.shape
         x = x.view(B * N, C, fH, fW)
@@ -571,7 +630,53 @@ class DepthLSSTransform(BaseDepthTransform):
             nn.Conv2d(in_channels, self.D + self.C, 1))
         self.downsample = _downsample_block(out_channels, downsample)
 
+    def cam_nets_served(self):
+        net = self.depthnet
+        if not cam_nets.depth_stem_structure(self.dtransform) or not isinstance(net, nn.Sequential) or len(net) != 7:
+            return False
+        for j, cin in ((0, self.in_channels + 64), (3, self.in_channels)):
+            conv = net[j]
+            if cam_nets.bias_layer_spec(conv, net[j + 1]) != ("conv", 3, 1) or not isinstance(net[j + 2], nn.ReLU):
+                return False
+            if (conv.in_channels, conv.out_channels) != (cin, self.in_channels):
+                return False
+        return self._head_served(net[6])
+
+    def _cam_nets_inputs(self, x, d):
+        """The depth raster: [B, N, 1, iH, iW] on the features' device, whose stem output is the feature map."""
+        if not (torch.is_tensor(d) and d.device == x.device and d.dim() == 5 and d.is_floating_point()
+                and tuple(d.shape[:3]) == (x.shape[0], x.shape[1], 1) and d.shape[3] >= 1 and d.shape[4] >= 1):
+            return False
+        if any(p.device != x.device for p in self.dtransform.parameters()):
+            return False
+        return cam_nets.stem_output_size(d.shape[3], d.shape[4]) == tuple(x.shape[3:])
+
+    def _cam_feats_fused(self, x, d):
+        """Five or six launches: the cast of the image features to channels-last 16-bit, the stem (two), the two 3x3 layers (the
+        first reads the stem's output and the image features as its two sources [d, x]: no cat), the head.  None where an entry
+        point refuses."""
+        B, N, C, fH, fW = x.shape
+        dtype, net = self.cam_nets_dtype, self.depthnet
+        xh = x.detach().reshape(B * N, C, fH, fW).to(dtype=dtype, memory_format=torch.channels_last)
+        (d,) = _fp32(d.detach())
+        dh = cam_nets.depth_stem_forward(d.reshape(B * N, d.shape[3], d.shape[4]).contiguous(),
+                                         cam_nets.fold_depth_stem(self.dtransform, dtype))
+        if dh is None:
+            return None
+        y = bev_conv_forward([dh, xh], cam_nets.fold_conv_bias_bn(net[0], net[1], dtype), out_layout="nhwc")
+        if y is None:
+            return None
+        y = bev_conv_forward([y], cam_nets.fold_conv_bias_bn(net[3], net[4], dtype), out_layout="nhwc")
+        if y is None:
+            return None
+        res = cam_nets.depth_head_forward(y, cam_nets.fold_depth_head(net[6], self.D, self.C, dtype))
+        return None if res is None else self._cam_feats_result(res[0], res[1], B, N)
+
     def get_cam_feats(self, x, d, *args):
+        if self.cam_nets_fusable(x, d):
+            res = self._cam_feats_fused(x, d)
+            if res is not None:
+                return res
         x, d = _fp32(x, d)
         B, N, C, fH, fW = x.shape
         d = d.view(B * N, *d.shape[2:])

@@ -253,6 +253,43 @@ int bevamd_bev_conv_forward(const void* src0, int channels0, const void* src1, i
                             int dst_channel_offset, int dst_layout, long long dst_elems, void* stream);
 
 
+/* The learned nets of the camera -> BEV view transform in eval mode (mmdet3d/models/vtransforms/depth_lss.py:43-97, lss.py:63-75)
+ * on 16-bit operands (dtype 0: fp16, 1: bf16) with fp32 accumulation on v_mfma_f32_16x16x32.  No device synchronisation, no
+ * allocation, no atomics, no split-K: equal calls give bit-equal results, a sample's result does not depend on the batch, and both
+ * calls can be captured in a graph.  Limits are checked on the host before any GPU work; batch 0 .. 65535 (0: nothing to do).
+ *
+ * bevamd_cam_depth_stem_forward (2 launches): DepthLSSTransform.dtransform, Conv2d(1, 8, 1), Conv2d(8, 32, 5, stride 4, padding 2),
+ *   Conv2d(32, 64, 5, stride 2, padding 2), each with bias, eval-mode BatchNorm2d and ReLU.  depth [batch, height, width] fp32
+ *   (depth_elems elements), read in place; out [batch, OH3, OW3, 64] NHWC 16-bit with OH2 = (height - 1) / 4 + 1, OH3 = (OH2 - 1) / 2
+ *   + 1 and the widths alike; scratch [batch, OH2, OW2, 32] 16-bit holds the layer-2 map (written in full, then read).  Both are
+ *   16-byte aligned and of exactly scratch_elems / out_elems elements.
+ *     a1[c]  = round16(max(fma(d, scale1[c], shift1[c]), 0))                         (never stored; fp32, one rounding)
+ *     a2[co] = round16(max(fma(sum_{tap, ci} w2 * a1, scale2[co], shift2[co]), 0))   a1 taken as ZERO outside the image
+ *     y[co]  = round16(max(fma(sum_{tap, ci} w3 * a2, scale3[co], shift3[co]), 0))   a2 taken as zero outside its map
+ *   scale_i = bn.weight / sqrt(running_var + eps), shift_i = bn.bias + (conv.bias - running_mean) * scale_i, fp32 arrays of 8, 32
+ *   and 64 floats (those of layers 2 and 3 16-byte aligned), never folded into the 16-bit weights.  packed2: exactly 32 * 224
+ *   elements, the A-fragment order of bevamd_bev_conv_forward for a 1 x 1 layer of 200 input channels k = 8 tap + ci (tap = 5 ky +
+ *   kx), zero for k >= 200; packed3: exactly 64 * 800 elements, the same order for the 5 x 5 layer of 32 channels.  Any height,
+ *   width >= 1.  Code 1: a null or misaligned pointer, a dtype other than 0 / 1, element counts that do not fit the sizes.
+ * bevamd_cam_depth_head_forward (1 launch): Conv2d(in_channels, depth_bins + context_channels, 1) with bias, softmax over the first
+ *   depth_bins rows, the split.  x [batch, height, width, in_channels] NHWC 16-bit, 16-byte aligned; packed: (depth_bins +
+ *   context_channels, rounded up to a multiple of 16) * in_channels elements in the same A-fragment order (1 x 1), zero rows past
+ *   the last; bias [depth_bins + context_channels] fp32.  depth [batch, depth_bins, height, width] fp32, context [batch, height,
+ *   width, context_channels] fp32, every element written, nothing else.  z = acc + bias in fp32, never stored;
+ *   depth = exp(z - max z) / sum exp(z - max z) over exactly the depth rows (expf within 1 ulp, IEEE division, the sum over a lane's
+ *   rows in ascending order, then over the four lane groups); context = z.  Served, anything else returns 4 (unsupported):
+ *   in_channels a multiple of 32 up to 512, depth_bins 1 .. 128, context_channels a multiple of 4 up to 128; any height, width >= 1.
+ *   Code 1 as above. */
+int bevamd_cam_depth_stem_forward(const float* depth, long long depth_elems, int batch, int height, int width, int dtype,
+                                  const float* scale1, const float* shift1, const void* packed2, long long packed2_elems,
+                                  const float* scale2, const float* shift2, const void* packed3, long long packed3_elems,
+                                  const float* scale3, const float* shift3, void* scratch, long long scratch_elems, void* out,
+                                  long long out_elems, void* stream);
+int bevamd_cam_depth_head_forward(const void* x, long long x_elems, int batch, int height, int width, int in_channels, int depth_bins,
+                                  int context_channels, int dtype, const void* packed, long long packed_elems, const float* bias,
+                                  float* depth, long long depth_elems, float* context, long long context_elems, void* stream);
+
+
 /* The non-learned end of CenterHead (mmdet3d/models/heads/bbox/centerpoint.py:637-884 get_bboxes / get_task_detections and
  * CenterPointBBoxCoder.decode, core/bbox/coders/centerpoint_bbox_coders.py:62-225).  Nothing below synchronises the device or
  * reads anything back; every call is a fixed number of launches on `stream` for ANY number of tasks and samples and can be
