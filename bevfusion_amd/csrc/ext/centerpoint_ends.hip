@@ -18,9 +18,9 @@
 //     boxes; per block of 64 rows all waves share the block's 64 x 63 / 2 pairs, wave `block` resolves the block greedily on a
 //     64-bit word, and every later live row tests itself against the rows the block kept.  No K x K mask, nothing leaves the device.
 // Circle tasks go through bevamd_circle_nms (head_ends.hip).
-// The rotated-overlap arithmetic is iou3d.hip's (iou3d_box.h), included before the pragma below so that both units evaluate it
-// under the same rules; everything after it is compiled with fp contract(off): products and sums round separately like the
-// reference's separate torch ops.  exp and atan2 are evaluated in double and rounded once.
+// The rotated-overlap arithmetic is iou3d.hip's (iou3d_box.h), which carries fp contract(off) in its own functions, so both units
+// evaluate it alike; everything after the pragma below is compiled with fp contract(off) too: products and sums round separately
+// like the reference's separate torch ops.  exp and atan2 are evaluated in double and rounded once.
 #include "common.h"
 #include "iou3d_box.h"
 #include "head_select.h"

@@ -25,8 +25,8 @@
 //   * targets_kernel  one workgroup: every row of labels / label_weights / bbox_targets / bbox_weights / ious, then num_pos and
 //                     matched_ious by a fixed-order LDS reduction.
 // No workspace, nothing read back, no atomics on float data: results are bit-equal from run to run.  Every output element is
-// written on every call.  The unit is compiled with fp contract(off) below iou3d_box.h (which is evaluated under the rules of
-// csrc/iou3d.hip); hipcc keeps fp32 divide correctly rounded.
+// written on every call.  The unit is compiled with fp contract(off), and so is iou3d_box.h by the pragma in each of its
+// functions (as in csrc/iou3d.hip); hipcc keeps fp32 divide correctly rounded.
 //
 // The solver cannot hang: one augmentation visits at most `cols` columns (a for loop over that bound), there are `rows`
 // augmentations, and the path walk back from the sink is a for loop over `rows + 1` steps; a problem that would need more ends with

@@ -17,8 +17,10 @@
 //   * NMS sweep ON THE DEVICE: one workgroup walks the row blocks; the greedy pass inside a block works on the 64
 //     diagonal words held in LDS, the surviving rows then OR their mask rows into the running `removed` words in parallel
 //     (coalesced across words).  No mask copy to the host, no malloc/free; the kept count can stay on the device.
-// Arithmetic follows the reference in fp32 (same tests, same EPS / MARGIN, same two-formula intersection); sinf / cosf /
-// atan2f are the device's, so results agree with the reference to rounding, not bit for bit (tolerance in the tests).
+// Arithmetic follows the reference in fp32 (same tests, same EPS / MARGIN, same two-formula intersection) with no FMA
+// contraction (iou3d_box.h carries fp contract(off) in every function: its sign tests on collinear edges need products that
+// round alike); sinf / cosf / atan2f are the device's, so results agree with the reference to rounding, not bit for bit
+// (tolerance in the tests).  The axis-aligned IoU below is compiled under the default rules.
 #include "common.h"
 #include "iou3d_box.h"
 

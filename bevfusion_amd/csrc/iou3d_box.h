@@ -1,7 +1,19 @@
-// Rotated-box BEV overlap arithmetic shared by csrc/iou3d.hip (pairwise IoU, NMS mask) and csrc/ext/centerpoint_ends.hip (the
-// segmented rotated NMS of CenterHead): one box's derived values, the reference's polygon-of-crossings overlap and the IoU
-// (iou3d_kernel.cu:126-229).  Device code only; a unit includes it BEFORE any `#pragma clang fp contract`, so that both units
-// evaluate it under the same floating-point rules.
+// Rotated-box BEV overlap arithmetic shared by csrc/iou3d.hip (pairwise IoU, NMS mask), csrc/ext/centerpoint_ends.hip (the
+// segmented rotated NMS of CenterHead) and csrc/ext/head_assign.hip (the IoU of the match cost): one box's derived values, the
+// reference's polygon-of-crossings overlap and the IoU (iou3d_kernel.cu:126-229).  Device code only.
+//
+// Every function opens with `#pragma clang fp contract(off)`: products and sums round separately, wherever a unit includes the
+// header.  The algorithm decides by the SIGN of differences of products (the strict straddle test s1 * s2 > 0 && s3 * s4 > 0, the
+// |s5 - s1| > EPS split) and on collinear edges those differences are exact zeros only when both products round alike.  Fused, one
+// product keeps its low bits and such a zero becomes a tiny number of either sign, so the tests can see crossings that are not
+// there.  Measured on an MI355X under the default contraction: boxes of equal size and yaw slid along their own axis came out up
+// to 0.12 off in IoU (6 of 1024 pairs), and the same rectangle written as (l, w, yaw + pi / 2) once came out as 7e9.  Un-fused,
+// the device's error against float64 equals the fp32 CPU restatement's to two digits on every family of tests/iou3d_families.py
+// (profiles/iou3d_families_parity_observed.json).  The pragma covers make_box, the centroid / atan2 keys and iou_rotated too, not
+// only the sign tests: the corners those tests read come from make_box's rotation, the CPU restatement that every bar and golden
+// keep set is stated against is built without contraction as a whole, and one rule for the header is what lets three units
+// include it anywhere.  What is left is the reference's own: on about 0.05 % of near-duplicate pairs the algorithm itself
+// returns finite, positive, meaningless values.
 #pragma once
 
 #include "common.h"
@@ -12,7 +24,10 @@ namespace iou3d {
 constexpr float EPS = 1e-8f;
 struct Pt { float x, y; };
 
-__device__ __forceinline__ float cross3(Pt p1, Pt p2, Pt p0) { return (p1.x - p0.x) * (p2.y - p0.y) - (p2.x - p0.x) * (p1.y - p0.y); }
+__device__ __forceinline__ float cross3(Pt p1, Pt p2, Pt p0) {
+#pragma clang fp contract(off)
+  return (p1.x - p0.x) * (p2.y - p0.y) - (p2.x - p0.x) * (p1.y - p0.y);
+}
 
 // everything that depends on one box only
 struct Box {
@@ -22,6 +37,7 @@ struct Box {
 };
 
 __device__ __forceinline__ Box make_box(const float* __restrict__ b) {
+#pragma clang fp contract(off)
   Box r;
   r.x1 = b[0]; r.y1 = b[1]; r.x2 = b[2]; r.y2 = b[3];
   const float ang = b[4];
@@ -40,6 +56,7 @@ __device__ __forceinline__ Box make_box(const float* __restrict__ b) {
 }
 
 __device__ __forceinline__ bool contains(const Box& b, Pt p) {
+#pragma clang fp contract(off)
   const float MARGIN = 1e-5f;
   const float cx = (b.x1 + b.x2) / 2, cy = (b.y1 + b.y2) / 2;
   const float rx = (p.x - cx) * b.cin + (p.y - cy) * b.sin_ + cx;
@@ -48,6 +65,7 @@ __device__ __forceinline__ bool contains(const Box& b, Pt p) {
 }
 
 __device__ __forceinline__ bool seg_intersection(Pt p1, Pt p0, Pt q1, Pt q0, Pt& ans) {
+#pragma clang fp contract(off)
   const bool rect = fminf(p0.x, p1.x) <= fmaxf(q0.x, q1.x) && fminf(q0.x, q1.x) <= fmaxf(p0.x, p1.x) &&
                     fminf(p0.y, p1.y) <= fmaxf(q0.y, q1.y) && fminf(q0.y, q1.y) <= fmaxf(p0.y, p1.y);
   if (!rect) return false;
@@ -68,6 +86,7 @@ __device__ __forceinline__ bool seg_intersection(Pt p1, Pt p0, Pt q1, Pt q0, Pt&
 }
 
 __device__ float overlap(const Box& A, const Box& B) {
+#pragma clang fp contract(off)
   Pt poly[16];
   float key[16];
   int cnt = 0;
@@ -120,6 +139,7 @@ __device__ float overlap(const Box& A, const Box& B) {
 }
 
 __device__ __forceinline__ float iou_rotated(const Box& A, const Box& B) {
+#pragma clang fp contract(off)
   const float sa = (A.x2 - A.x1) * (A.y2 - A.y1), sb = (B.x2 - B.x1) * (B.y2 - B.y1);
   const float so = overlap(A, B);
   return so / fmaxf(sa + sb - so, EPS);

@@ -494,7 +494,10 @@ def iou3d_nms(boxes_sorted, thresh, normal=False):
 
 def rotated_overlap_float64(box_a, box_b):
     """Independent check of the overlap area: Sutherland-Hodgman clipping of the two rotated rectangles in float64
-    (not the reference's algorithm; agrees with it away from degenerate contacts)."""
+    (not the reference's algorithm; agrees with it away from degenerate contacts).  A vertex is inside a clip edge when
+    its signed distance d to the edge is >= 0; a crossing is emitted only between vertices on different sides, at
+    t = d_prev / (d_prev - d_cur), whose denominator is the sum of two magnitudes of which one is positive: it cannot
+    vanish, however close to parallel the two edges are.  A box with a non-finite corner encloses no area."""
     def corners(bx):
         x1, y1, x2, y2, ang = [float(v) for v in bx]
         cx, cy = (x1 + x2) / 2, (y1 + y2) / 2
@@ -507,24 +510,34 @@ def rotated_overlap_float64(box_a, box_b):
         return 0.5 * sum(poly[i][0] * poly[(i + 1) % len(poly)][1] - poly[(i + 1) % len(poly)][0] * poly[i][1]
                          for i in range(len(poly)))
 
-    subj, clip = corners(box_a), corners(box_b)
+    with np.errstate(invalid="ignore"):
+        subj, clip = corners(box_a), corners(box_b)
+    if not all(np.isfinite(v) for pt in subj + clip for v in pt):
+        return 0.0
     if area(clip) < 0:
         clip = clip[::-1]
     for i in range(4):
         p, q = clip[i], clip[(i + 1) % 4]
         if not subj:
             break
-        inside = lambda r: (q[0] - p[0]) * (r[1] - p[1]) - (q[1] - p[1]) * (r[0] - p[0]) >= 0  # noqa: E731
+        ex, ey = q[0] - p[0], q[1] - p[1]
+        dist = [ex * (r[1] - p[1]) - ey * (r[0] - p[0]) for r in subj]
         out = []
         for j in range(len(subj)):
-            cur, prev = subj[j], subj[j - 1]
-            if inside(cur) != inside(prev):
-                d1 = (q[0] - p[0], q[1] - p[1])
-                d2 = (cur[0] - prev[0], cur[1] - prev[1])
-                den = d1[0] * d2[1] - d1[1] * d2[0]
-                t = ((prev[0] - p[0]) * d2[1] - (prev[1] - p[1]) * d2[0]) / den
-                out.append((p[0] + t * d1[0], p[1] + t * d1[1]))
-            if inside(cur):
+            cur, prev, d_cur, d_prev = subj[j], subj[j - 1], dist[j], dist[j - 1]
+            if (d_prev >= 0) != (d_cur >= 0):
+                t = d_prev / (d_prev - d_cur)
+                out.append((prev[0] + t * (cur[0] - prev[0]), prev[1] + t * (cur[1] - prev[1])))
+            if d_cur >= 0:
                 out.append(cur)
         subj = out
     return abs(area(subj)) if len(subj) >= 3 else 0.0
+
+
+def rotated_iou_float64(box_a, box_b):
+    """iou_bev (iou3d_kernel.cu:224-229) in float64 from the fp32 box values: overlap / max(sa + sb - overlap, 1e-8)."""
+    a, b = [float(v) for v in box_a], [float(v) for v in box_b]
+    sa, sb = (a[2] - a[0]) * (a[3] - a[1]), (b[2] - b[0]) * (b[3] - b[1])
+    ov = rotated_overlap_float64(box_a, box_b)
+    union = sa + sb - ov
+    return ov / (union if union > 1e-8 else 1e-8)          # like fmaxf, a NaN union gives the floor

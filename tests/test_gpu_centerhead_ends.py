@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 import torch
 
+import iou3d_families as families
 from bevfusion_amd import heads, iou3d
 from conftest import record_parity
 from test_centerhead_ends import (TIE_CFG, case_preds, check_case, check_decode, check_sync, gen, get_bboxes, gold, tie_coder,  # noqa: F401
@@ -73,6 +74,34 @@ def test_segmented_nms_keeps_the_rows_of_nms_sorted(dev):
         assert torch.equal(torch.nonzero(keep[s])[:, 0], rows) and int(counts[s]) == len(rows) and 1 < len(rows) < R
     host, _ = heads.rotate_nms_segments(b.cpu(), None, 0.3)
     assert torch.equal(keep.cpu(), host)
+
+
+def test_segmented_nms_on_clusters_of_duplicates(dev):
+    """Detector-like input (tests/iou3d_families.clusters: objects 12 m apart with 1 .. 12 copies each, among them bit-exact
+    duplicates, yaw + pi and sizes exchanged with yaw + pi / 2), rows in descending score, one segment with a third of its rows
+    not live.  At 0.2 the kept rows are the first live copy of every object, which needs no oracle; they are also the rows of
+    iou3d.nms_sorted over the live rows and of the host path."""
+    S, R, thr = 3, 130, 0.2
+    boxes, objs = np.zeros((S, R, 7), np.float32), np.zeros((S, R), np.int64)
+    for s in range(S):
+        b5, scores, obj = families.clusters(R, seed=families.SEGMENT_SEEDS[s])
+        order = np.argsort(-scores, kind="stable")
+        boxes[s], objs[s] = families.lift(b5[order]), obj[order]
+        intra = families.intra_cluster_ious(families.lidar_bev(boxes[s]), objs[s])
+        assert intra.min() > thr + 1e-3, "a cluster pair sits within 1e-3 of the threshold: choose another seed"
+    live = np.ones((S, R), bool)
+    live[1, np.random.default_rng(4).choice(R, R // 3, replace=False)] = False
+    b, lv = torch.from_numpy(boxes).to(dev), torch.from_numpy(live).to(dev)
+    keep, counts = heads.rotate_nms_segments(b, lv, thr)
+    for s in range(S):
+        rows = np.nonzero(live[s])[0]
+        truth = rows[np.unique(objs[s][rows], return_index=True)[1]]       # first live row of every object
+        got = torch.nonzero(keep[s])[:, 0].cpu().numpy()
+        assert np.array_equal(got, np.sort(truth)) and int(counts[s]) == len(truth) and 1 < len(truth) < len(rows)
+        sorted_rows = iou3d.nms_sorted(heads._lidar_bev_xyxyr(b[s][lv[s]]), thr).cpu().numpy()
+        assert np.array_equal(rows[sorted_rows], got)
+    host, host_counts = heads.rotate_nms_segments(b.cpu(), lv.cpu(), thr)
+    assert torch.equal(keep.cpu(), host) and torch.equal(counts.cpu(), host_counts)
 
 
 def test_more_than_1024_rows_per_segment_raise(dev):

@@ -20,6 +20,8 @@ import pytest
 import torch
 from scipy.optimize import linear_sum_assignment
 
+import iou3d_families as families
+import oracle
 from bevfusion_amd import head_assign, head_targets, heads
 from conftest import record_parity
 from test_head_assign import (CASES, ROWWISE, check_targets, cost_errors, gen, gold, host_mirror, make_assigner, make_coder,  # noqa: F401
@@ -355,3 +357,59 @@ def test_assigner_and_cost_classes(gold, bars, dev):
         assert np.abs(total.cpu().numpy() - cost[b, 0, :, :G]).max() <= 2.4e-7   # the same terms, summed by torch: one fp32 ulp below 2
     empty = assigner.assign(torch.from_numpy(boxes[0]).to(dev), gt[0][0][:0], gt[1][0][:0], preds["heatmap"][:1], cfg)
     assert empty.num_gts == 0 and empty.max_overlaps is None and not empty.gt_inds.any().item()
+
+
+# ---- ha_iou3d on near-duplicate, collinear and far-away boxes against float64 (tests/iou3d_families.py) ---------------------------
+@pytest.fixture(scope="module")
+def lifted_refs():
+    """Per family, lifted to LiDAR boxes (z = -1, height 1.5): the float64 3D IoU o h / (va + vb - o h) with o from
+    oracle.rotated_overlap_float64, the same from the fp32 oracle's o, the well-conditioned mask and the device's allowance."""
+    return {name: families.reference_lifted(name) for name in families.FAMILIES}
+
+
+@pytest.mark.parametrize("name", families.FAMILIES)
+def test_bbox_overlaps_on_family_pairs_stay_within_four_oracle_errors_of_float64(name, lifted_refs, dev):
+    """The bars of test_gpu_iou3d.py's family test, through BboxOverlaps3D: pair p is the diagonal of the [P, P] result."""
+    r = lifted_refs[name]
+    a, b = torch.from_numpy(r["a7"]).to(dev), torch.from_numpy(r["b7"]).to(dev)
+    calc = head_assign.BboxOverlaps3D()
+    full = calc(a, b)
+    assert torch.equal(full, calc(a, b)), f"{name}: two calls differ"
+    full = full.cpu().numpy()
+    got, well, allowed = np.diagonal(full).astype(np.float64), r["well"], r["bar_iou"]
+    assert not np.isnan(got).any() and (got >= 0).all(), f"{name}: NaN or negative on the diagonal"
+    err = np.abs(got - r["iou64"])
+    worst = float(err[well].max())
+    print(f"{name}: device 3D IoU max error against float64 {worst:.3g} on {int(well.sum())} well-conditioned pairs (allowed "
+          f"{allowed:.3g}; oracle {r['oracle_err_iou']:.3g}); {int((err[well] > allowed).sum())} over; "
+          f"{int((~well).sum())} ill-conditioned")
+    record_parity(f"iou3d_family/{name}/device_iou3d_vs_f64", worst, allowed)
+    assert worst <= allowed, f"{name}: {worst} > {allowed} at pair {int(np.argmax(np.where(well, err, 0)))}"
+    # off the diagonal: ordinary pairs against the fp32 oracle's overlap under the same 3D formula, 1e-4
+    o = oracle.iou3d_pairwise(families.lidar_bev(r["a7"]), families.lidar_bev(r["b7"]), "overlap").astype(np.float64) * 1.5
+    va, vb = np.prod(r["a7"][:, 3:6].astype(np.float64), 1), np.prod(r["b7"][:, 3:6].astype(np.float64), 1)
+    want = o / np.maximum(va[:, None] + vb[None, :] - o, 1e-8)
+    off = ~np.eye(families.P, dtype=bool)
+    assert np.max(np.abs(full[off] - want[off])) <= 1e-4
+
+
+def test_bbox_overlaps_on_special_boxes_have_the_oracles_nans(dev):
+    """The 16 special pairs lifted to LiDAR boxes (a zero-area box, a negative extent and so a negative volume, a NaN yaw, an inf
+    coordinate, which lifts to an inf centre and size and a NaN edge, yaw = 1e4): NaN where the fp32 oracle's overlap put through
+    the same 3D formula in fp32 has NaN, on all 256 entries; within 1e-4 of it on the 16 pairs where both are finite (the other
+    entries pair two degenerate boxes, see test_gpu_iou3d.py); the same on a second call."""
+    A, B = families.special()
+    a7, b7 = families.lift(A), families.lift(B)
+    a, b = torch.from_numpy(a7).to(dev), torch.from_numpy(b7).to(dev)
+    calc = head_assign.BboxOverlaps3D()
+    got_t = calc(a, b)
+    assert torch.equal(got_t.view(torch.int32), calc(a, b).view(torch.int32)), "two calls differ"
+    got = got_t.cpu().numpy()
+    with np.errstate(invalid="ignore", over="ignore"):
+        o = oracle.iou3d_pairwise(families.lidar_bev(a7), families.lidar_bev(b7), "overlap") * np.float32(1.5)
+        va, vb = a7[:, 3] * a7[:, 4] * a7[:, 5], b7[:, 3] * b7[:, 4] * b7[:, 5]
+        want = o / np.fmax(va[:, None] + vb[None, :] - o, np.float32(1e-8))        # fmaxf: a NaN union gives the floor
+    assert want.dtype == np.float32 and np.array_equal(np.isnan(got), np.isnan(want))
+    pairs = np.isfinite(np.diagonal(got)) & np.isfinite(np.diagonal(want))
+    assert pairs.sum() >= 10 and np.array_equal(np.isfinite(np.diagonal(got)), np.isfinite(np.diagonal(want)))
+    assert np.max(np.abs(np.diagonal(got)[pairs] - np.diagonal(want)[pairs])) <= 1e-4
