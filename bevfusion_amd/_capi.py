@@ -174,6 +174,8 @@ _EXT_SIGNATURES = {
     # CenterHead: the fused task heads
     "bevamd_center_heads_forward": (I, [P, I, I, I, I, I, I, I, P, P, P, LL, P, LL, P]),
     "bevamd_bev_conv_forward": (I, [P, I, P, I, I, I, I, I, I, I, I, I, I, P, LL, P, P, P, I, I, I, LL, P]),
+    # camera necks: resampling + cat + convolution + BatchNorm + ReLU
+    "bevamd_neck_conv_forward": (I, [P, I, I, I, I, P, I, I, I, I, I, I, I, I, I, I, P, LL, P, P, I, P, I, I, I, LL, P]),
     # camera depth nets: the depth stem and the depthnet's softmax head
     "bevamd_cam_depth_stem_forward": (I, [P, LL, I, I, I, I, P, P, P, LL, P, P, P, LL, P, P, P, LL, P, LL, P]),
     "bevamd_cam_depth_head_forward": (I, [P, LL, I, I, I, I, I, I, I, P, LL, P, P, LL, P, LL, P]),

@@ -24,7 +24,9 @@ mmdet3d/core/bbox/coders/transfusion_bbox_coder.py, mmdet3d/core/post_processing
   * `ConvFuser`, `SECOND`, `SECONDFPN`, `bev_conv_forward`, `fold_bev_layer`: the dense BEV trunk in front of the heads as modules
     and its fused convolution + BatchNorm + ReLU layer for eval mode, re-exported from `bev_trunk`;
   * `fold_conv_bias_bn`, `fold_depth_stem`, `fold_depth_head`, `depth_stem_forward`, `depth_head_forward`: the learned nets of the
-    camera view transforms on 16-bit operands, re-exported from `cam_nets`.
+    camera view transforms on 16-bit operands, re-exported from `cam_nets`;
+  * `GeneralizedLSSFPN`, `LSSFPN`, `cam_neck_conv_forward`, `fold_conv_bias`: the camera necks as modules and their fused
+    resampling + `cat` + convolution + BatchNorm + ReLU layer for eval mode, re-exported from `cam_neck`.
 
 Dispatch: device tensors go through the library or raise (no torch formulation for them); host tensors run the reference's
 formulation written in torch / numpy with a STABLE descending argsort, which is the order the kernels are defined to produce
@@ -44,6 +46,8 @@ from .bev_trunk import (SECOND, SECONDFPN, ConvFuser, FoldedBevLayer, bev_conv_f
                         bev_unpack_weight, fold_bev_layer)
 from .cam_nets import (DepthHeadFold, DepthStemFold, depth_head_forward, depth_stem_forward, fold_conv_bias_bn,  # noqa: F401
                        fold_depth_head, fold_depth_stem)                    # (the camera depth nets)
+from .cam_neck import (LSSFPN, GeneralizedLSSFPN, cam_neck_conv_forward, fold_conv_bias, fold_neck_layer,  # noqa: F401
+                       neck_layer_spec)                                     # (the camera necks)
 from .centerhead import CenterPointBBoxCoder, centerhead_get_bboxes, rotate_nms_segments  # noqa: F401  (the CenterHead end)
 from .decoder import MultiheadAttention, PositionEmbeddingLearned, TransformerDecoderLayer, fused_attention  # noqa: F401  (the decoder layer)
 from .head_targets import centerhead_get_targets, transfusion_heatmap_targets  # noqa: F401  (the training targets)
@@ -67,7 +71,8 @@ __all__ = ["circle_nms", "circle_nms_segments", "TransFusionBBoxCoder", "Proposa
            "head_class_encoding", "head_ffn_forward", "HEADS", "CenterHead", "SeparateHead", "FoldedCenterHeads", "center_heads_forward",
            "center_heads_pack_w1", "center_heads_unpack_w1", "fold_center_heads", "ConvFuser", "SECOND", "SECONDFPN", "FoldedBevLayer",
            "bev_conv_forward", "bev_pack_weight", "bev_unpack_weight", "fold_bev_layer", "DepthStemFold", "DepthHeadFold",
-           "fold_conv_bias_bn", "fold_depth_stem", "fold_depth_head", "depth_stem_forward", "depth_head_forward"]
+           "fold_conv_bias_bn", "fold_depth_stem", "fold_depth_head", "depth_stem_forward", "depth_head_forward", "GeneralizedLSSFPN",
+           "LSSFPN", "cam_neck_conv_forward", "fold_conv_bias", "fold_neck_layer", "neck_layer_spec"]
 
 MAX_PROPOSALS = 1024     # HE_MAX_K of the kernels: proposals per sample, rows per NMS segment
 _UNSUPPORTED = 4

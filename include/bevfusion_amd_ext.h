@@ -253,6 +253,45 @@ int bevamd_bev_conv_forward(const void* src0, int channels0, const void* src1, i
                             int dst_channel_offset, int dst_layout, long long dst_elems, void* stream);
 
 
+/* One layer of the camera necks in eval mode (mmdet3d/models/necks/generalized_lss.py GeneralizedLSSFPN, models/necks/lss.py
+ * LSSFPN): F.interpolate(bilinear, align_corners=True) + torch.cat + convolution + folded BatchNorm + optional ReLU in ONE launch
+ * on 16-bit storage (dtype 0: fp16, 1: bf16) with fp32 accumulation on v_mfma_f32_16x16x32; no workspace, no device
+ * synchronisation, no atomics, no split-K: equal calls give bit-equal results, a sample's result does not depend on the batch, and
+ * the call can be captured in a graph.
+ *
+ * bevamd_neck_conv_forward: src0 [batch, channels0, height0, width0] and, when channels1 > 0, src1 [batch, channels1, height1,
+ *   width1], each contiguous in its OWN layout (0: NCHW, 1: NHWC = [batch, h, w, c]; an NHWC source is 16-byte aligned) and with
+ *   its OWN map.  The layer's input at the output resolution [out_height, out_width] is the channel concatenation of R(src0) then
+ *   R(src1).  R is the identity (a copy, no arithmetic) for a source whose map equals the output map; otherwise the bilinear
+ *   resampling with align_corners=True in exactly this fp32 arithmetic, no FMA contraction (h, w: the source's map, H, W: the
+ *   output's, (Y, X) the output pixel):
+ *     ry = H > 1 ? (float)(h - 1) / (float)(H - 1) : 0                                              (rx likewise)
+ *     sy = ry * (float)Y;  y0 = min((int)sy, h - 1);  y1 = y0 + (y0 < h - 1);  ly = sy - (float)y0;  hy = 1.f - ly   (x likewise)
+ *     v  = hy * (hx * a[y0][x0] + lx * a[y0][x1]) + ly * (hx * a[y1][x0] + lx * a[y1][x1])
+ *   v is rounded ONCE to the storage type and that 16-bit value is the MFMA operand; any ratio is served, downsampling included.
+ *   kernel 1 or 3, stride 1, padding kernel / 2: the zero padding applies AFTER the resampling (positions outside the output map
+ *   are zero).  With Cin = channels0 + channels1 and nch = ceil(Cin / 32), packed holds exactly packed_elems = out_channels * nch *
+ *   kernel^2 * 32 16-bit elements, 16-byte aligned, in the A-fragment order of bevamd_bev_conv_forward (mode 0).  scale, shift:
+ *   [out_channels] fp32, 16-byte aligned, never folded into the 16-bit weights.
+ *     y[b, co, p] = round16(relu ? max(fma(acc, scale[co], shift[co]), 0) : fma(acc, scale[co], shift[co]))
+ *   with ONE fp32 accumulator chain per element in ascending (chunk, tap, ci).  y is written into the channels
+ *   [dst_channel_offset, dst_channel_offset + out_channels) of dst [batch, dst_channels_total, out_height, out_width] in dst_layout
+ *   (dst_elems = batch * dst_channels_total * out_height * out_width elements; an NHWC dst is 8-byte aligned); exactly that window
+ *   is written, nothing else, and the sources are only read inside their extents.  Limits, checked on the host before any GPU
+ *   work, anything else returns 4 (unsupported): kernel 1 or 3, channels0 a multiple of 16 (>= 16), channels1 0 or a multiple of
+ *   16, out_channels a multiple of 32, an NHWC destination with dst_channels_total and dst_channel_offset in multiples of 4.  All
+ *   maps >= 1 x 1 and at most 2^31 - 1 pixels; batch 0 .. 65535 (0: nothing to do).  Code 1: a null or misaligned pointer, a bad
+ *   layout or dtype, bad sizes, packed_elems or dst_elems that do not fit the layer.  The entry takes no extents of the sources,
+ *   of scale and of shift and cannot tell a host pointer from a device pointer: the caller guarantees device buffers of batch *
+ *   channels * height * width elements per source and out_channels floats each for scale and shift (the Python wrapper checks
+ *   both and refuses host tensors). */
+int bevamd_neck_conv_forward(const void* src0, int channels0, int height0, int width0, int layout0, const void* src1, int channels1,
+                             int height1, int width1, int layout1, int dtype, int batch, int out_height, int out_width,
+                             int out_channels, int kernel, const void* packed, long long packed_elems, const float* scale,
+                             const float* shift, int relu, void* dst, int dst_channels_total, int dst_channel_offset, int dst_layout,
+                             long long dst_elems, void* stream);
+
+
 /* The learned nets of the camera -> BEV view transform in eval mode (mmdet3d/models/vtransforms/depth_lss.py:43-97, lss.py:63-75)
  * on 16-bit operands (dtype 0: fp16, 1: bf16) with fp32 accumulation on v_mfma_f32_16x16x32.  No device synchronisation, no
  * allocation, no atomics, no split-K: equal calls give bit-equal results, a sample's result does not depend on the batch, and both
