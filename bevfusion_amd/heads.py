@@ -26,7 +26,10 @@ mmdet3d/core/bbox/coders/transfusion_bbox_coder.py, mmdet3d/core/post_processing
   * `fold_conv_bias_bn`, `fold_depth_stem`, `fold_depth_head`, `depth_stem_forward`, `depth_head_forward`: the learned nets of the
     camera view transforms on 16-bit operands, re-exported from `cam_nets`;
   * `GeneralizedLSSFPN`, `LSSFPN`, `cam_neck_conv_forward`, `fold_conv_bias`: the camera necks as modules and their fused
-    resampling + `cat` + convolution + BatchNorm + ReLU layer for eval mode, re-exported from `cam_neck`.
+    resampling + `cat` + convolution + BatchNorm + ReLU layer for eval mode, re-exported from `cam_neck`;
+  * `GeneralizedResNet`, `BasicBlock`, `make_res_layer`, `res_block_forward`, `fold_res_block`, `res_block_spec`: the residual BEV
+    backbone of the camera configs as a module and its fused block tail (conv2 + BatchNorm + residual + ReLU) for eval mode,
+    re-exported from `bev_resnet`.
 
 Dispatch: device tensors go through the library or raise (no torch formulation for them); host tensors run the reference's
 formulation written in torch / numpy with a STABLE descending argsort, which is the order the kernels are defined to produce
@@ -44,6 +47,8 @@ from torch.nn import functional as F
 from . import _capi
 from .bev_trunk import (SECOND, SECONDFPN, ConvFuser, FoldedBevLayer, bev_conv_forward, bev_pack_weight,  # noqa: F401  (the BEV trunk)
                         bev_unpack_weight, fold_bev_layer)
+from .bev_resnet import (BasicBlock, FoldedResBlock, GeneralizedResNet, fold_res_block, make_res_layer,  # noqa: F401
+                         res_block_forward, res_block_spec)                 # (the residual BEV backbone)
 from .cam_nets import (DepthHeadFold, DepthStemFold, depth_head_forward, depth_stem_forward, fold_conv_bias_bn,  # noqa: F401
                        fold_depth_head, fold_depth_stem)                    # (the camera depth nets)
 from .cam_neck import (LSSFPN, GeneralizedLSSFPN, cam_neck_conv_forward, fold_conv_bias, fold_neck_layer,  # noqa: F401
@@ -72,7 +77,8 @@ __all__ = ["circle_nms", "circle_nms_segments", "TransFusionBBoxCoder", "Proposa
            "center_heads_pack_w1", "center_heads_unpack_w1", "fold_center_heads", "ConvFuser", "SECOND", "SECONDFPN", "FoldedBevLayer",
            "bev_conv_forward", "bev_pack_weight", "bev_unpack_weight", "fold_bev_layer", "DepthStemFold", "DepthHeadFold",
            "fold_conv_bias_bn", "fold_depth_stem", "fold_depth_head", "depth_stem_forward", "depth_head_forward", "GeneralizedLSSFPN",
-           "LSSFPN", "cam_neck_conv_forward", "fold_conv_bias", "fold_neck_layer", "neck_layer_spec"]
+           "LSSFPN", "cam_neck_conv_forward", "fold_conv_bias", "fold_neck_layer", "neck_layer_spec", "GeneralizedResNet", "BasicBlock",
+           "make_res_layer", "FoldedResBlock", "fold_res_block", "res_block_forward", "res_block_spec"]
 
 MAX_PROPOSALS = 1024     # HE_MAX_K of the kernels: proposals per sample, rows per NMS segment
 _UNSUPPORTED = 4

@@ -253,6 +253,41 @@ int bevamd_bev_conv_forward(const void* src0, int channels0, const void* src1, i
                             int dst_channel_offset, int dst_layout, long long dst_elems, void* stream);
 
 
+/* The second half of a ResNet BasicBlock in eval mode (mmdet3d/models/backbones/resnet.py GeneralizedResNet over mmcv's BasicBlock):
+ * conv2 3x3 + folded bn2 + residual + ReLU in ONE launch on 16-bit storage (dtype 0: fp16, 1: bf16) with fp32 accumulation on
+ * v_mfma_f32_16x16x32; no workspace, no device synchronisation, no atomics, no split-K: equal calls give bit-equal results, a
+ * sample's result does not depend on the batch, and the call can be captured in a graph.
+ *
+ * bevamd_res_block_forward: h [batch, channels, out_height, out_width] (the output of conv1 + bn1 + ReLU) in h_layout and x
+ *   [batch, x_channels, x_height, x_width] (the block's input) in x_layout (0: NCHW, 1: NHWC = [batch, height, width, c]), both
+ *   contiguous; an NHWC tensor is 16-byte aligned.  residual 0 (identity): x_channels = channels, x's map equals the output's and
+ *   stride is 1; packed_d, scale_d and shift_d are not read (null, packed_d_elems 0).  residual 1 (downsample): a 1 x 1
+ *   convolution of x with stride 1 or 2 and no padding, out_height = (x_height - 1) / stride + 1 and the width alike.
+ *   packed2 holds exactly packed2_elems = channels * (channels / 32) * 9 * 32 16-bit elements and packed_d exactly packed_d_elems =
+ *   channels * ceil(x_channels / 32) * 32, both 16-byte aligned, in the A-fragment order of bevamd_bev_conv_forward (mode 0,
+ *   kernel 3 and kernel 1; zero where ci >= x_channels).  scale2, shift2, scale_d, shift_d: [channels] fp32, 16-byte aligned
+ *   (scale = bn.weight / sqrt(running_var + eps), shift = bn.bias - running_mean * scale; never folded into the 16-bit weights).
+ *     v = fma(sum_{chunk, tap, ci} w2 * h, scale2[co], shift2[co])                    h zero outside the map
+ *     r = (float)x[b, co, p]                                                          (identity)
+ *     r = fma(sum_{chunk, ci} wd * x[b, ci, stride * p], scale_d[co], shift_d[co])    (downsample)
+ *     y[b, co, p] = round16(max(v + r, 0))
+ *   in fp32 without contraction, ONE accumulator chain per sum in ascending (chunk, tap, ci).  dst [batch, channels, out_height,
+ *   out_width] in dst_layout (dst_elems = batch * channels * out_height * out_width elements; an NHWC dst is 8-byte aligned):
+ *   every element is written, nothing else, and h and x are only read inside their extents.  dst must not overlap h or x.
+ *   Limits, checked on the host before any GPU work, anything else returns 4 (unsupported): residual 0 or 1, stride 1 or 2,
+ *   channels a multiple of 32 (>= 32), x_channels a multiple of 16 (>= 16).  All maps >= 1 x 1; batch 0 .. 65535 (0: nothing to
+ *   do, the tensors may be null).  Code 1: a null or misaligned pointer, a bad layout or dtype, bad sizes, maps that do not match
+ *   the stride, an identity residual whose x differs from the output's shape, packed2_elems, packed_d_elems or dst_elems that do
+ *   not fit the block, a dst that overlaps h or x.  The entry takes no extents of h, x, the scales and the shifts and cannot tell
+ *   a host pointer from a device pointer: the caller guarantees device buffers of the sizes above (the Python wrapper checks
+ *   them and refuses host tensors). */
+int bevamd_res_block_forward(const void* h, int h_layout, const void* x, int x_layout, int x_channels, int x_height, int x_width,
+                             int dtype, int batch, int channels, int out_height, int out_width, int residual, int stride,
+                             const void* packed2, long long packed2_elems, const float* scale2, const float* shift2,
+                             const void* packed_d, long long packed_d_elems, const float* scale_d, const float* shift_d, void* dst,
+                             int dst_layout, long long dst_elems, void* stream);
+
+
 /* One layer of the camera necks in eval mode (mmdet3d/models/necks/generalized_lss.py GeneralizedLSSFPN, models/necks/lss.py
  * LSSFPN): F.interpolate(bilinear, align_corners=True) + torch.cat + convolution + folded BatchNorm + optional ReLU in ONE launch
  * on 16-bit storage (dtype 0: fp16, 1: bf16) with fp32 accumulation on v_mfma_f32_16x16x32; no workspace, no device
