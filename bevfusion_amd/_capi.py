@@ -176,6 +176,9 @@ _EXT_SIGNATURES = {
     "bevamd_bev_conv_forward": (I, [P, I, P, I, I, I, I, I, I, I, I, I, I, P, LL, P, P, P, I, I, I, LL, P]),
     # GeneralizedResNet: the BasicBlock tail, conv2 + BatchNorm + residual (identity or 1x1 downsample) + ReLU
     "bevamd_res_block_forward": (I, [P, I, P, I, I, I, I, I, I, I, I, I, I, I, P, LL, P, P, P, LL, P, P, P, I, LL, P]),
+    # camera ResNet: the Bottleneck tail (conv3 + BatchNorm + residual + ReLU) and the stem (conv 7x7 + BatchNorm + ReLU + MaxPool)
+    "bevamd_bottleneck_tail_forward": (I, [P, I, I, P, I, I, I, I, I, I, I, I, I, I, I, P, LL, P, P, P, LL, P, P, P, I, LL, P]),
+    "bevamd_resnet_stem_forward": (I, [P, I, I, I, I, I, I, I, I, I, I, I, I, I, P, LL, P, P, P, I, LL, P]),
     # camera necks: resampling + cat + convolution + BatchNorm + ReLU
     "bevamd_neck_conv_forward": (I, [P, I, I, I, I, P, I, I, I, I, I, I, I, I, I, I, P, LL, P, P, I, P, I, I, I, LL, P]),
     # camera depth nets: the depth stem and the depthnet's softmax head

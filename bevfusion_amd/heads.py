@@ -29,7 +29,11 @@ mmdet3d/core/bbox/coders/transfusion_bbox_coder.py, mmdet3d/core/post_processing
     resampling + `cat` + convolution + BatchNorm + ReLU layer for eval mode, re-exported from `cam_neck`;
   * `GeneralizedResNet`, `BasicBlock`, `make_res_layer`, `res_block_forward`, `fold_res_block`, `res_block_spec`: the residual BEV
     backbone of the camera configs as a module and its fused block tail (conv2 + BatchNorm + residual + ReLU) for eval mode,
-    re-exported from `bev_resnet`.
+    re-exported from `bev_resnet`;
+  * `ResNet`, `Bottleneck`, `bottleneck_tail_forward`, `fold_bottleneck`, `bottleneck_spec`, `stem_forward`, `fold_stem`,
+    `stem_spec`, `stem_pack_weight`, `stem_unpack_weight`: the camera backbone of the ResNet-50 configs as a module and its fused
+    Bottleneck tail (conv3 + BatchNorm + residual + ReLU) and stem (conv 7x7 + BatchNorm + ReLU + MaxPool) for eval mode,
+    re-exported from `cam_resnet`.
 
 Dispatch: device tensors go through the library or raise (no torch formulation for them); host tensors run the reference's
 formulation written in torch / numpy with a STABLE descending argsort, which is the order the kernels are defined to produce
@@ -49,6 +53,8 @@ from .bev_trunk import (SECOND, SECONDFPN, ConvFuser, FoldedBevLayer, bev_conv_f
                         bev_unpack_weight, fold_bev_layer)
 from .bev_resnet import (BasicBlock, FoldedResBlock, GeneralizedResNet, fold_res_block, make_res_layer,  # noqa: F401
                          res_block_forward, res_block_spec)                 # (the residual BEV backbone)
+from .cam_resnet import (Bottleneck, FoldedBottleneckTail, FoldedStem, ResNet, bottleneck_spec, bottleneck_tail_forward,  # noqa: F401
+                         fold_bottleneck, fold_stem, stem_forward, stem_pack_weight, stem_spec, stem_unpack_weight)  # (the camera ResNet)
 from .cam_nets import (DepthHeadFold, DepthStemFold, depth_head_forward, depth_stem_forward, fold_conv_bias_bn,  # noqa: F401
                        fold_depth_head, fold_depth_stem)                    # (the camera depth nets)
 from .cam_neck import (LSSFPN, GeneralizedLSSFPN, cam_neck_conv_forward, fold_conv_bias, fold_neck_layer,  # noqa: F401
@@ -78,7 +84,9 @@ __all__ = ["circle_nms", "circle_nms_segments", "TransFusionBBoxCoder", "Proposa
            "bev_conv_forward", "bev_pack_weight", "bev_unpack_weight", "fold_bev_layer", "DepthStemFold", "DepthHeadFold",
            "fold_conv_bias_bn", "fold_depth_stem", "fold_depth_head", "depth_stem_forward", "depth_head_forward", "GeneralizedLSSFPN",
            "LSSFPN", "cam_neck_conv_forward", "fold_conv_bias", "fold_neck_layer", "neck_layer_spec", "GeneralizedResNet", "BasicBlock",
-           "make_res_layer", "FoldedResBlock", "fold_res_block", "res_block_forward", "res_block_spec"]
+           "make_res_layer", "FoldedResBlock", "fold_res_block", "res_block_forward", "res_block_spec",
+           "ResNet", "Bottleneck", "FoldedBottleneckTail", "FoldedStem", "bottleneck_spec", "fold_bottleneck", "bottleneck_tail_forward",
+           "stem_spec", "fold_stem", "stem_forward", "stem_pack_weight", "stem_unpack_weight"]
 
 MAX_PROPOSALS = 1024     # HE_MAX_K of the kernels: proposals per sample, rows per NMS segment
 _UNSUPPORTED = 4

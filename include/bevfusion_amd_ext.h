@@ -288,6 +288,69 @@ int bevamd_res_block_forward(const void* h, int h_layout, const void* x, int x_l
                              int dst_layout, long long dst_elems, void* stream);
 
 
+/* The tail of a ResNet Bottleneck in eval mode (mmdet 2.x mmdet/models/backbones/resnet.py, the camera backbone `ResNet`): conv3
+ * 1x1 + folded bn3 + residual + ReLU in ONE launch on 16-bit storage (dtype 0: fp16, 1: bf16) with fp32 accumulation on
+ * v_mfma_f32_16x16x32; no workspace, no device synchronisation, no atomics, no split-K: equal calls give bit-equal results, a
+ * sample's result does not depend on the batch, and the call can be captured in a graph.
+ *
+ * bevamd_bottleneck_tail_forward: h [batch, planes, out_height, out_width] (the output of conv2 + bn2 + ReLU) in h_layout and x
+ *   [batch, x_channels, x_height, x_width] (the block's input) in x_layout (0: NCHW, 1: NHWC = [batch, height, width, c]), both
+ *   contiguous; an NHWC tensor is 16-byte aligned.  residual 0 (identity): x_channels = channels, x's map equals the output's and
+ *   stride is 1; packed_d, scale_d and shift_d are not read (null, packed_d_elems 0).  residual 1 (downsample): a 1 x 1
+ *   convolution of x with stride 1 or 2 and no padding, out_height = (x_height - 1) / stride + 1 and the width alike.
+ *   packed3 holds exactly packed3_elems = channels * ceil(planes / 32) * 32 16-bit elements and packed_d exactly packed_d_elems =
+ *   channels * ceil(x_channels / 32) * 32, both 16-byte aligned, in the A-fragment order of bevamd_bev_conv_forward (mode 0,
+ *   kernel 1; zero where ci >= planes or x_channels).  scale3, shift3, scale_d, shift_d: [channels] fp32, 16-byte aligned
+ *   (scale = bn.weight / sqrt(running_var + eps), shift = bn.bias - running_mean * scale; never folded into the 16-bit weights).
+ *     v = fma(sum_{chunk, ci} w3 * h[b, ci, p], scale3[co], shift3[co])
+ *     r = (float)x[b, co, p]                                                          (identity)
+ *     r = fma(sum_{chunk, ci} wd * x[b, ci, stride * p], scale_d[co], shift_d[co])    (downsample)
+ *     y[b, co, p] = round16(max(v + r, 0))
+ *   in fp32 without contraction, ONE accumulator chain per sum in ascending (chunk, ci).  dst [batch, channels, out_height,
+ *   out_width] in dst_layout (dst_elems = batch * channels * out_height * out_width elements; an NHWC dst is 8-byte aligned):
+ *   every element is written, nothing else, and h and x are only read inside their extents.  dst must not overlap h or x.
+ *   channels need not equal 4 * planes.
+ *   Limits, checked on the host before any GPU work, anything else returns 4 (unsupported): residual 0 or 1, stride 1 or 2,
+ *   channels a multiple of 32 (>= 32), planes and x_channels multiples of 16 (>= 16).  All maps >= 1 x 1; batch 0 .. 65535 (0:
+ *   nothing to do, the tensors may be null); batch * out_height * out_width below 2^31 - 128.  Code 1: a null or misaligned
+ *   pointer, a bad layout or dtype, bad sizes, maps that do not match the stride, an identity residual whose x differs from the
+ *   output's shape, packed3_elems, packed_d_elems or dst_elems that do not fit the block, a dst that overlaps h or x.  The entry
+ *   takes no extents of h, x, the scales and the shifts and cannot tell a host pointer from a device pointer: the caller
+ *   guarantees device buffers of the sizes above (the Python wrapper checks them and refuses host tensors). */
+int bevamd_bottleneck_tail_forward(const void* h, int h_layout, int planes, const void* x, int x_layout, int x_channels, int x_height,
+                                   int x_width, int dtype, int batch, int channels, int out_height, int out_width, int residual,
+                                   int stride, const void* packed3, long long packed3_elems, const float* scale3, const float* shift3,
+                                   const void* packed_d, long long packed_d_elems, const float* scale_d, const float* shift_d,
+                                   void* dst, int dst_layout, long long dst_elems, void* stream);
+
+
+/* The stem of a ResNet in eval mode (mmdet 2.x ResNet.forward: conv1, norm1, relu, maxpool): convolution 7 x 7 stride 2 padding 3
+ * from 3 to 64 channels + folded BatchNorm + ReLU + max pooling 3 x 3 stride 2 padding 1 in ONE launch on 16-bit storage (dtype 0:
+ * fp16, 1: bf16) with fp32 accumulation on v_mfma_f32_16x16x32; the convolution's map never reaches memory; no workspace, no
+ * device synchronisation, no atomics: equal calls give bit-equal results, a sample's result does not depend on the batch, and the
+ * call can be captured in a graph.
+ *
+ * bevamd_resnet_stem_forward: x [batch, 3, height, width] contiguous NCHW.  OH = (height - 1) / 2 + 1, PH = (OH - 1) / 2 + 1, the
+ *   widths alike.  packed holds exactly packed_elems = 4 * 6 * 64 * 8 = 12288 16-bit elements, 16-byte aligned: element
+ *   [mt][kstep][lane][j] is w[co = 16 mt + (lane & 15)][ci][ky][kx = j] with 7 ci + ky = 4 kstep + (lane >> 4), zero where kx = 7
+ *   or 7 ci + ky >= 21.  scale, shift: [64] fp32, 16-byte aligned, as for bevamd_res_block_forward.
+ *     c[b, co, cy, cx] = round16(max(fma(sum_k w * x[b, ci, 2 cy - 3 + ky, 2 cx - 3 + kx], scale[co], shift[co]), 0))
+ *     y[b, co, ph, pw] = max over the cells (2 ph - 1 + dy, 2 pw - 1 + dx), dy, dx in 0 .. 2, inside the OH x OW map, of c
+ *   x zero outside the image; fp32 without contraction, ONE accumulator chain per c in ascending k = 8 (7 ci + ky) + kx.  Rounding
+ *   is monotone, so y equals the maximum of the fp32 values rounded once.  dst [batch, 64, PH, PW] in dst_layout (0: NCHW, 1:
+ *   NHWC, then 16-byte aligned; dst_elems = batch * 64 * PH * PW): every element is written, nothing else, and x is only read
+ *   inside its extent.  dst must not overlap x.
+ *   Limits, checked on the host before any GPU work, anything else returns 4 (unsupported): in_channels 3, out_channels 64,
+ *   kernel 7, stride 2, padding 3; pool_kernel 3, pool_stride 2, pool_padding 1, pool_ceil_mode 0.  Image >= 1 x 1; batch 0 ..
+ *   65535 (0: nothing to do, x and dst may be null).  Code 1: a null or misaligned pointer, a bad layout or dtype, bad sizes,
+ *   packed_elems or dst_elems that do not fit, a dst that overlaps x.  The entry takes no extents of x, scale and shift: the
+ *   caller guarantees device buffers of the sizes above (the Python wrapper checks them and refuses host tensors). */
+int bevamd_resnet_stem_forward(const void* x, int dtype, int batch, int in_channels, int height, int width, int out_channels,
+                               int kernel, int stride, int padding, int pool_kernel, int pool_stride, int pool_padding,
+                               int pool_ceil_mode, const void* packed, long long packed_elems, const float* scale,
+                               const float* shift, void* dst, int dst_layout, long long dst_elems, void* stream);
+
+
 /* One layer of the camera necks in eval mode (mmdet3d/models/necks/generalized_lss.py GeneralizedLSSFPN, models/necks/lss.py
  * LSSFPN): F.interpolate(bilinear, align_corners=True) + torch.cat + convolution + folded BatchNorm + optional ReLU in ONE launch
  * on 16-bit storage (dtype 0: fp16, 1: bf16) with fp32 accumulation on v_mfma_f32_16x16x32; no workspace, no device
