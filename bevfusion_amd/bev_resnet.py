@@ -31,7 +31,8 @@ import torch
 from torch import nn
 
 from . import _capi
-from .bev_trunk import _DTYPES, _as_source, _fusable_tensor, _fused_layer, _is_nhwc, _no_grad_needed, bev_pack_weight, layer_spec
+from .bev_trunk import (_DTYPES, _as_source, _empty, _fusable_tensor, _fused_layer, _is_nhwc, _no_grad_needed, _tensor_key, bev_pack_weight,
+                        layer_spec)
 from .registry import BACKBONES, register_everywhere  # noqa: F401
 
 __all__ = ["GeneralizedResNet", "BasicBlock", "make_res_layer", "FoldedResBlock", "fold_res_block", "res_block_forward",
@@ -172,7 +173,7 @@ def fold_res_block(block):
     tensors = [block.conv2.weight] + ([block.downsample[0].weight] if block.downsample is not None else [])
     for bn in bns:
         tensors += [bn.weight, bn.bias, bn.running_mean, bn.running_var]
-    key = tuple((t.data_ptr(), t._version, t.dtype, t.device) if t is not None else None for t in tensors) + tuple(bn.eps for bn in bns)
+    key = _tensor_key(tensors) + tuple(bn.eps for bn in bns)
     cache = block.__dict__.get("_bevamd_folded")
     if cache is not None and cache[0] == key:
         return cache[1]
@@ -222,10 +223,7 @@ def res_block_forward(h, x, fold, *, out_layout="nhwc"):
                            f"{fold.residual}, stride {s})")
     h, h_nhwc = _layout(h, "h")
     x, x_nhwc = _layout(x, "x")
-    if out_layout == "nhwc":
-        out = torch.empty((B, OH, OW, C), dtype=h.dtype, device=dev).permute(0, 3, 1, 2)
-    else:
-        out = torch.empty((B, C, OH, OW), dtype=h.dtype, device=dev)
+    out = _empty((B, C, OH, OW), h.dtype, dev, out_layout)
     with torch.cuda.device(dev):
         rc = _capi.load().bevamd_res_block_forward(
             _capi.ptr(h), h_nhwc, _capi.ptr(x), x_nhwc, Cx, Hx, Wx, _DTYPES[h.dtype], B, C, OH, OW, int(down), s,

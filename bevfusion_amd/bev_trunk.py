@@ -159,13 +159,18 @@ def fold_bev_layer(conv, bn):
     through `.data` does not, and after one the cache has to be dropped by hand (`del conv._bevamd_folded`).  Run one forward before
     capturing a graph: a fold computed inside a capture is filled only when the graph replays."""
     tensors = [conv.weight, bn.weight, bn.bias, bn.running_mean, bn.running_var]
-    key = tuple((t.data_ptr(), t._version, t.dtype, t.device) if t is not None else None for t in tensors) + (bn.eps,)
+    key = _tensor_key(tensors) + (bn.eps,)
     cache = conv.__dict__.get("_bevamd_folded")
     if cache is not None and cache[0] == key:
         return cache[1]
     val = _fold(conv, bn)
     conv.__dict__["_bevamd_folded"] = (key, val)
     return val
+
+
+def _tensor_key(tensors):
+    """What a cached fold is keyed on: the tensors' addresses and versions (None for an absent one)."""
+    return tuple((t.data_ptr(), t._version, t.dtype, t.device) if t is not None else None for t in tensors)
 
 
 # ---- the kernel ------------------------------------------------------------------------------------------------------------------
@@ -177,6 +182,14 @@ def _as_source(t):
     """A tensor the kernel reads in place: contiguous NCHW or channels-last strides; anything else is made contiguous NCHW."""
     t = t.detach()
     return t if t.is_contiguous() or _is_nhwc(t) else t.contiguous()
+
+
+def _empty(shape, dtype, dev, out_layout):
+    """A fresh logical [B, C, H, W]: channels-last strides for "nhwc", contiguous otherwise."""
+    B, C, H, W = shape
+    if out_layout == "nhwc":
+        return torch.empty((B, H, W, C), dtype=dtype, device=dev).permute(0, 3, 1, 2)
+    return torch.empty((B, C, H, W), dtype=dtype, device=dev)
 
 
 def bev_conv_forward(srcs, fold, *, stride=None, mode=None, out=None, out_channel_offset=0, out_layout="nhwc"):
@@ -222,10 +235,7 @@ def bev_conv_forward(srcs, fold, *, stride=None, mode=None, out=None, out_channe
     else:
         OH, OW = (H + 2 * (fold.kernel // 2) - fold.kernel) // fold.stride + 1, (W + 2 * (fold.kernel // 2) - fold.kernel) // fold.stride + 1
     if out is None:
-        if out_layout == "nhwc":
-            out = torch.empty((B, OH, OW, fold.out_channels), dtype=x0.dtype, device=dev).permute(0, 3, 1, 2)
-        else:
-            out = torch.empty((B, fold.out_channels, OH, OW), dtype=x0.dtype, device=dev)
+        out = _empty((B, fold.out_channels, OH, OW), x0.dtype, dev, out_layout)
     if out.device != dev or out.dtype != x0.dtype or out.dim() != 4 or out.shape[0] != B or tuple(out.shape[2:]) != (OH, OW):
         raise RuntimeError(f"out must be a {x0.dtype} [{B}, C, {OH}, {OW}] on the device of the sources, got {tuple(out.shape)} {out.dtype}")
     if out.is_contiguous():

@@ -39,7 +39,7 @@ from torch import nn
 from torch.nn import functional as F
 
 from . import _capi
-from .bev_trunk import (FoldedBevLayer, _DTYPES, _as_source, _fusable_tensor, _is_nhwc, _no_grad_needed, bev_conv_forward,
+from .bev_trunk import (FoldedBevLayer, _DTYPES, _as_source, _empty, _fusable_tensor, _is_nhwc, _no_grad_needed, bev_conv_forward,
                         bev_pack_weight, fold_bev_layer)
 from .cam_nets import _bn_ok, _cached, _plain_conv, fold_conv_bias_bn
 from .registry import NECKS, register_everywhere  # noqa: F401
@@ -148,10 +148,7 @@ def cam_neck_conv_forward(srcs, fold, *, out_size=None, relu=True, out=None, out
     layouts = [0 if t.is_contiguous() else 1 for t in srcs]
     B = x0.shape[0]
     if out is None:
-        if out_layout == "nhwc":
-            out = torch.empty((B, OH, OW, fold.out_channels), dtype=x0.dtype, device=dev).permute(0, 3, 1, 2)
-        else:
-            out = torch.empty((B, fold.out_channels, OH, OW), dtype=x0.dtype, device=dev)
+        out = _empty((B, fold.out_channels, OH, OW), x0.dtype, dev, out_layout)
     if out.device != dev or out.dtype != x0.dtype or out.dim() != 4 or out.shape[0] != B or tuple(out.shape[2:]) != (OH, OW):
         raise RuntimeError(f"out must be a {x0.dtype} [{B}, C, {OH}, {OW}] on the device of the sources, got {tuple(out.shape)} {out.dtype}")
     if out.is_contiguous():

@@ -23,14 +23,13 @@ import torch
 from torch import nn
 
 from . import _capi
-from .bev_trunk import FoldedBevLayer, bev_pack_weight
+from .bev_trunk import _DTYPES, FoldedBevLayer, _tensor_key, bev_pack_weight
 
 __all__ = ["DepthStemFold", "DepthHeadFold", "fold_conv_bias_bn", "fold_depth_stem", "fold_depth_head", "depth_stem_forward",
            "depth_head_forward", "depth_stem_structure", "bias_layer_spec", "stem_output_size", "head_served", "pack_stem_layer2",
            "pack_head_weight"]
 
 _UNSUPPORTED = 4          # BEVAMD_ERR_UNSUPPORTED
-_DTYPES = {torch.float16: 0, torch.bfloat16: 1}
 HEAD_MAX_IN, HEAD_MAX_D, HEAD_MAX_C = 512, 128, 128
 _STEM = [(1, 8, 1, 1, 0), (8, 32, 5, 4, 2), (32, 64, 5, 2, 2)]        # (in, out, kernel, stride, padding) of dtransform's layers
 
@@ -102,7 +101,7 @@ def _scale_shift(conv, bn):
 def _cached(owner, slot, dtype, tensors, extra, make):
     """`make()` cached on `owner` per dtype, keyed on the tensors' addresses and versions (see `bev_trunk.fold_bev_layer`: every
     in-place torch operation moves the version; after a write through `.data` drop the cache by hand)."""
-    key = tuple((t.data_ptr(), t._version, t.dtype, t.device) if t is not None else None for t in tensors) + tuple(extra)
+    key = _tensor_key(tensors) + tuple(extra)
     store = owner.__dict__.setdefault(slot, {})
     hit = store.get(dtype)
     if hit is not None and hit[0] == key:

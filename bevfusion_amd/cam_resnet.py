@@ -37,7 +37,8 @@ from torch import nn
 
 from . import _capi
 from .bev_resnet import BasicBlock, _bn_served, _layout, _scale_shift, _tail_class, fold_res_block, res_block_forward, res_block_spec
-from .bev_trunk import _DTYPES, _as_source, _fusable_tensor, _fused_layer, _is_nhwc, _no_grad_needed, bev_pack_weight, layer_spec
+from .bev_trunk import (_DTYPES, _as_source, _empty, _fusable_tensor, _fused_layer, _is_nhwc, _no_grad_needed, _tensor_key, bev_pack_weight,
+                        layer_spec)
 from .registry import BACKBONES, build_conv_layer, build_norm_layer, register_everywhere  # noqa: F401
 
 __all__ = ["ResNet", "Bottleneck", "FoldedBottleneckTail", "FoldedStem", "bottleneck_spec", "fold_bottleneck",
@@ -160,7 +161,7 @@ class FoldedBottleneckTail:
 
 
 def _cache_key(tensors, bns):
-    return tuple((t.data_ptr(), t._version, t.dtype, t.device) if t is not None else None for t in tensors) + tuple(bn.eps for bn in bns)
+    return _tensor_key(tensors) + tuple(bn.eps for bn in bns)
 
 
 def _fold_tail(block):
@@ -195,13 +196,6 @@ def fold_bottleneck(block):
     val = _fold_tail(block)
     block.__dict__["_bevamd_folded_tail"] = (key, val)
     return val
-
-
-def _empty(shape, dtype, dev, out_layout):
-    B, C, H, W = shape
-    if out_layout == "nhwc":
-        return torch.empty((B, H, W, C), dtype=dtype, device=dev).permute(0, 3, 1, 2)
-    return torch.empty((B, C, H, W), dtype=dtype, device=dev)
 
 
 def bottleneck_tail_forward(h, x, fold, *, out_layout="nhwc"):

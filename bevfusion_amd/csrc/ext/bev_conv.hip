@@ -5,38 +5,22 @@
 //   mmdet3d/models/backbones/second.py:93-97 SECOND.forward: per layer Conv2d 3x3 (stride 1 or 2) + BatchNorm2d + ReLU
 //   mmdet3d/models/necks/second.py:93-98     SECONDFPN.forward: per level Conv2d / ConvTranspose2d + BatchNorm2d + ReLU, torch.cat
 //
-// Native formulation: an implicit GEMM D[channel][pixel] = W[channel][(chunk, tap, ci)] * X[(chunk, tap, ci)][pixel] on
-// v_mfma_f32_16x16x32_{f16,bf16} with fp32 accumulation.
+// Native formulation: the dense conv tile of dense_tile.h.
 //   * A workgroup of four waves owns 8 x 16 output pixels x 32 * MT output channels (MT = 1, 2 or 4): wave w owns the channel half
 //     w & 1 (MT tiles of 16 channels) and the four pixel rows 4 (w >> 1) ..; every pixel row of 16 is one MFMA column tile.
-//   * The haloed input tile ((8 - 1) s + k) x ((16 - 1) s + k) pixels is staged in LDS in chunks of 32 channels as
-//     [pixel][32 channels + 8 of padding], so a lane's B fragment (8 channels of one pixel) is one 16-byte LDS read and all k x k
-//     taps read the same chunk from shifted addresses.  The next chunk is loaded from memory into registers while the current one
-//     is multiplied (one LDS buffer, two barriers per chunk).  Cells outside the map and channels past the last source are zero in
-//     LDS; no address outside the tensors is formed.
+//   * The haloed input tile ((8 - 1) s + k) x ((16 - 1) s + k) pixels is staged chunk by chunk.  The next chunk is loaded from
+//     memory into registers while the current one is multiplied (one LDS buffer, two barriers per chunk).
 //   * Up to two sources are read as one channel-concatenated input (every staged group of 8 channels lies in one source), each
-//     NCHW or NHWC; an NCHW source is transposed while staging (eight 2-byte loads along the channel, one 16-byte LDS write).
-//   * The weights are packed on the host in A-fragment order (one 16-byte load per lane and MFMA) and stream from L2.
-//   * Epilogue: y = max(fma(acc, scale[co], shift[co]), 0) in fp32, rounded once to the storage type, written into the channel
-//     window [dst_off, dst_off + cout) of an NHWC (8-byte stores of 4 channels) or NCHW destination.
+//     NCHW or NHWC.
+//   * Epilogue: y = max(fma(acc, scale[co], shift[co]), 0), written into the channel window [dst_off, dst_off + cout) of an NHWC
+//     or NCHW destination.
 //   * A deconvolution with kernel = stride = 2 is four 1 x 1 products (blockIdx.y carries the tap) written to (2y + dy, 2x + dx).
-// Every output element is ONE accumulator chain in ascending (chunk, tap, ci): no atomics, no split-K; equal calls give equal bits
-// and a sample's result does not depend on the batch around it.
-#include "common.h"
-
-#pragma clang fp contract(off)
+// Equal calls give equal bits and a sample's result does not depend on the batch around it.
+#include "dense_tile.h"
 
 namespace bevamd {
 
-typedef float bc_f32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 bc_f16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bc_bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned int bc_u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int bc_u32x2 __attribute__((ext_vector_type(2)));
-
 constexpr int BC_TH = 8, BC_TW = 16;          // output pixels of one workgroup
-constexpr int BC_CK = 32;                     // channels of one staged chunk = one MFMA k-step per tap
-constexpr int BC_PSTR = BC_CK + 8;            // 16-bit elements per pixel in LDS (80 bytes: the padding spreads the banks)
 constexpr int BC_THREADS = 256;
 
 struct BcArgs {
@@ -53,29 +37,13 @@ struct BcArgs {
   int dst_c, dst_off, dst_nhwc;
 };
 
-template <bool BF16>
-__device__ __forceinline__ bc_f32x4 bc_mfma(bc_u32x4 a, bc_u32x4 b, bc_f32x4 acc) {
-  if constexpr (BF16)
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bc_bf16x8, a), __builtin_bit_cast(bc_bf16x8, b), acc, 0, 0, 0);
-  else
-    return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(bc_f16x8, a), __builtin_bit_cast(bc_f16x8, b), acc, 0, 0, 0);
-}
-
-template <bool BF16>
-__device__ __forceinline__ unsigned short bc_round(float v) {
-  if constexpr (BF16)
-    return __builtin_bit_cast(unsigned short, (__bf16)v);
-  else
-    return __builtin_bit_cast(unsigned short, (_Float16)v);
-}
-
 template <bool BF16, int MT, int KS, int S>
 __global__ __launch_bounds__(BC_THREADS) void bev_conv_kernel(BcArgs a) {
   constexpr int P = KS / 2, TAPS = KS * KS;
   constexpr int IH = (BC_TH - 1) * S + KS, IW = (BC_TW - 1) * S + KS;   // the haloed input tile
-  constexpr int NPIX = IH * IW, UNITS = NPIX * (BC_CK / 8);             // a unit: 8 channels of one pixel, 16 bytes
+  constexpr int NPIX = IH * IW, UNITS = NPIX * (CK / 8);             // a unit: 8 channels of one pixel, 16 bytes
   constexpr int UPT = (UNITS + BC_THREADS - 1) / BC_THREADS;
-  __shared__ __attribute__((aligned(16))) unsigned short xs[NPIX * BC_PSTR];
+  __shared__ __attribute__((aligned(16))) unsigned short xs[NPIX * PSTR];
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int ty = blockIdx.x / a.tiles_x, tx = blockIdx.x - ty * a.tiles_x;
@@ -87,34 +55,23 @@ __global__ __launch_bounds__(BC_THREADS) void bev_conv_kernel(BcArgs a) {
   const int ctot = a.c0 + a.c1;
   const size_t hw = (size_t)a.H * a.W;
 
-  bc_u32x4 pre[UPT];
+  u32x4 pre[UPT];
   auto load_chunk = [&](int ch) {
 #pragma unroll
     for (int u = 0; u < UPT; ++u) {
       const int idx = tid + u * BC_THREADS;
-      bc_u32x4 v = {0u, 0u, 0u, 0u};
+      u32x4 v = {0u, 0u, 0u, 0u};
       if (idx < UNITS) {
-        int p, grp;
-        if (a.src_nhwc) { grp = idx & 3; p = idx >> 2; } else { grp = idx / NPIX; p = idx - grp * NPIX; }
-        const int iy = p / IW, ix = p - iy * IW;
+        const Unit un = unit_of<NPIX>(idx, a.src_nhwc);
+        const int iy = un.p / IW, ix = un.p - iy * IW;
         const int gy = iy0 + iy, gx = ix0 + ix;
-        const int c = ch * BC_CK + grp * 8;
+        const int c = ch * CK + un.grp * 8;
         if (gy >= 0 && gy < a.H && gx >= 0 && gx < a.W && c < ctot) {
           const bool first = c < a.c0;
           const unsigned short* src = first ? a.src0 : a.src1;
           const int cc = first ? c : c - a.c0, cs = first ? a.c0 : a.c1;
-          if (a.src_nhwc) {
-            v = *reinterpret_cast<const bc_u32x4*>(src + (((size_t)b * a.H + gy) * a.W + gx) * cs + cc);
-          } else {
-            const unsigned short* q = src + ((size_t)b * cs + cc) * hw + (size_t)gy * a.W + gx;
-            unsigned int e[8];
-#pragma unroll
-            for (int j = 0; j < 8; ++j) e[j] = q[(size_t)j * hw];
-            v[0] = e[0] | (e[1] << 16);
-            v[1] = e[2] | (e[3] << 16);
-            v[2] = e[4] | (e[5] << 16);
-            v[3] = e[6] | (e[7] << 16);
-          }
+          if (a.src_nhwc) v = *reinterpret_cast<const u32x4*>(src + (((size_t)b * a.H + gy) * a.W + gx) * cs + cc);
+          else v = gather8(src + ((size_t)b * cs + cc) * hw + (size_t)gy * a.W + gx, hw);
         }
       }
       pre[u] = v;
@@ -125,9 +82,8 @@ __global__ __launch_bounds__(BC_THREADS) void bev_conv_kernel(BcArgs a) {
     for (int u = 0; u < UPT; ++u) {
       const int idx = tid + u * BC_THREADS;
       if (idx < UNITS) {
-        int p, grp;
-        if (a.src_nhwc) { grp = idx & 3; p = idx >> 2; } else { grp = idx / NPIX; p = idx - grp * NPIX; }
-        *reinterpret_cast<bc_u32x4*>(xs + p * BC_PSTR + grp * 8) = pre[u];
+        const Unit un = unit_of<NPIX>(idx, a.src_nhwc);
+        *reinterpret_cast<u32x4*>(xs + un.p * PSTR + un.grp * 8) = pre[u];
       }
     }
   };
@@ -136,16 +92,16 @@ __global__ __launch_bounds__(BC_THREADS) void bev_conv_kernel(BcArgs a) {
   const int lr = lane & 15, lg = lane >> 4;
   const int mt0 = ctile * (2 * MT) + mh * MT;            // the wave's first tile of 16 channels
   // A fragment of (group g, channel tile mt, chunk, tap): 64 lanes x 16 bytes
-  const bc_u32x4* wp = reinterpret_cast<const bc_u32x4*>(a.packed) + ((size_t)(g * (a.cout / 16) + mt0) * a.nch) * (TAPS * 64) + lane;
+  const u32x4* wp = reinterpret_cast<const u32x4*>(a.packed) + ((size_t)(g * (a.cout / 16) + mt0) * a.nch) * (TAPS * 64) + lane;
   const size_t wtile = (size_t)a.nch * (TAPS * 64);
   // B fragment: lane holds X[k = 8 lg + j][pixel lr] of pixel row r0 + n
-  const unsigned short* xb = xs + ((r0 * S) * IW + lr * S) * BC_PSTR + lg * 8;
+  const unsigned short* xb = xs + ((r0 * S) * IW + lr * S) * PSTR + lg * 8;
 
-  bc_f32x4 acc[MT][4];
+  f32x4 acc[MT][4];
 #pragma unroll
   for (int m = 0; m < MT; ++m)
 #pragma unroll
-    for (int n = 0; n < 4; ++n) acc[m][n] = bc_f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int n = 0; n < 4; ++n) acc[m][n] = f32x4{0.f, 0.f, 0.f, 0.f};
 
   load_chunk(0);
 #pragma unroll 1
@@ -153,32 +109,17 @@ __global__ __launch_bounds__(BC_THREADS) void bev_conv_kernel(BcArgs a) {
     store_chunk();
     __syncthreads();
     if (ch + 1 < a.nch) load_chunk(ch + 1);
-#pragma unroll
-    for (int tap = 0; tap < TAPS; ++tap) {
-      const int ky = tap / KS, kx = tap % KS;
-      bc_u32x4 af[MT], bf[4];
-#pragma unroll
-      for (int m = 0; m < MT; ++m) af[m] = wp[(size_t)m * wtile + (size_t)(ch * TAPS + tap) * 64];
-#pragma unroll
-      for (int n = 0; n < 4; ++n) bf[n] = *reinterpret_cast<const bc_u32x4*>(xb + ((n * S + ky) * IW + kx) * BC_PSTR);
-#pragma unroll
-      for (int m = 0; m < MT; ++m)
-#pragma unroll
-        for (int n = 0; n < 4; ++n) acc[m][n] = bc_mfma<BF16>(af[m], bf[n], acc[m][n]);
-    }
+    chunk_mma<BF16, MT, KS, S, IW>(acc, wp, wtile, ch, xb);
     __syncthreads();   // the next chunk overwrites the tile
   }
 
-  // D fragment: pixel on the lane (lr), channel = 16 tile + 4 lg + reg
   const int dy = a.up == 2 ? g >> 1 : 0, dx = a.up == 2 ? g & 1 : 0;
   const int OHt = a.OH * a.up, OWt = a.OW * a.up;
   const int ox = ox0 + lr;
 #pragma unroll
   for (int m = 0; m < MT; ++m) {
     const int co = (mt0 + m) * 16 + lg * 4;
-    const float4 sc = *reinterpret_cast<const float4*>(a.scale + co);
-    const float4 sh = *reinterpret_cast<const float4*>(a.shift + co);
-    const float s4[4] = {sc.x, sc.y, sc.z, sc.w}, t4[4] = {sh.x, sh.y, sh.z, sh.w};
+    const Affine4 bn = load_affine4(a.scale, a.shift, co);
 #pragma unroll
     for (int n = 0; n < 4; ++n) {
       const int oy = oy0 + r0 + n;
@@ -186,15 +127,9 @@ __global__ __launch_bounds__(BC_THREADS) void bev_conv_kernel(BcArgs a) {
       const int Y = oy * a.up + dy, X = ox * a.up + dx;
       unsigned short r[4];
 #pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const float v = fmaf(acc[m][n][q], s4[q], t4[q]);
-        r[q] = bc_round<BF16>(v > 0.f ? v : 0.f);
-      }
+      for (int q = 0; q < 4; ++q) r[q] = round16<BF16>(relu(affine(acc[m][n][q], bn, q)));
       if (a.dst_nhwc) {
-        bc_u32x2 o;
-        o[0] = (unsigned int)r[0] | ((unsigned int)r[1] << 16);
-        o[1] = (unsigned int)r[2] | ((unsigned int)r[3] << 16);
-        *reinterpret_cast<bc_u32x2*>(a.dst + (((size_t)b * OHt + Y) * OWt + X) * a.dst_c + a.dst_off + co) = o;
+        *reinterpret_cast<u32x2*>(a.dst + (((size_t)b * OHt + Y) * OWt + X) * a.dst_c + a.dst_off + co) = pack4(r[0], r[1], r[2], r[3]);
       } else {
         unsigned short* d = a.dst + (((size_t)b * a.dst_c + a.dst_off + co) * OHt + Y) * OWt + X;
 #pragma unroll
@@ -263,8 +198,8 @@ int bevamd_bev_conv_forward(const void* src0, int channels0, const void* src1, i
   const int up = deconv ? 2 : 1, groups = up * up, taps = deconv ? 1 : kernel * kernel;
   const int OH = deconv ? height : (height + 2 * (kernel / 2) - kernel) / stride + 1;
   const int OW = deconv ? width : (width + 2 * (kernel / 2) - kernel) / stride + 1;
-  const int nch = (channels0 + channels1 + BC_CK - 1) / BC_CK;
-  const long long want_packed = (long long)groups * out_channels * nch * taps * BC_CK;
+  const int nch = (channels0 + channels1 + CK - 1) / CK;
+  const long long want_packed = (long long)groups * out_channels * nch * taps * CK;
   BEVAMD_REQUIRE(packed_elems == want_packed, "bev_conv_forward: packed holds %lld elements, this layer needs %lld", packed_elems, want_packed);
   const long long want_dst = (long long)batch * dst_channels_total * (OH * up) * (long long)(OW * up);
   BEVAMD_REQUIRE(dst_elems == want_dst, "bev_conv_forward: dst holds %lld elements, [%d, %d, %d, %d] needs %lld", dst_elems, batch,

@@ -5,39 +5,25 @@
 //   with downsample = Sequential(Conv2d 1x1 stride 1 or 2, BatchNorm2d): five (identity) or seven launches over the widest maps of
 //   the camera backbone, every intermediate written and read once.
 //
-// Native formulation: the implicit GEMM of res_block.hip without a halo (D[channel][pixel] on v_mfma_f32_16x16x32_{f16,bf16}, fp32
-// accumulation).
+// Native formulation: the dense conv tile of dense_tile.h without a halo.
 //   * The output pixels of the whole batch are ONE flat index p = (b OH + oy) OW + ox.  A workgroup of four waves owns 128
 //     consecutive p x 32 * MT output channels (MT = 1, 2 or 4): wave w owns the channel half w & 1 and the 64 pixels 64 (w >> 1) ..,
 //     four MFMA column tiles of 16.  A tile may span two samples; a pixel's result depends on nothing but its own column.
-//   * Phase 1 (acc3): the 128 pixels of h are staged in LDS in chunks of 32 channels as [pixel][32 + 8].  Phase 2 (accd, downsample
-//     mode only): the 128 pixels (b, s oy, s ox) of x are staged into the same buffer and multiplied by the 1 x 1 weight into a
-//     SECOND accumulator set.  In both phases the next chunk (the first chunk of x after the last of h) is loaded from memory into
-//     registers while the current one is multiplied.  Pixels past the last and channels past the source's last are zero in LDS; no
-//     address outside a tensor is formed.
-//   * h, x and dst carry their own layout (NCHW sources are transposed while staging).  The weights come packed in A-fragment order
-//     (bev_pack_weight with one tap) and stream from L2.
-//   * Epilogue, fp32, no contraction: v = fma(acc3, scale3, shift3); r = x at the lane's own pixel and four channels (identity) or
+//   * Phase 1 (acc3): the 128 pixels of h are staged chunk by chunk.  Phase 2 (accd, downsample mode only): the 128 pixels
+//     (b, s oy, s ox) of x are staged into the same buffer and multiplied by the 1 x 1 weight into a SECOND accumulator set.  In
+//     both phases the next chunk (the first chunk of x after the last of h) is loaded from memory into registers while the current
+//     one is multiplied.  Pixels past the last are zero in LDS.
+//   * h, x and dst carry their own layout.  The weights come from bev_pack_weight with one tap.
+//   * Epilogue: v = fma(acc3, scale3, shift3); r = x at the lane's own pixel and four channels (identity) or
 //     r = fma(accd, scale_d, shift_d); y = max(v + r, 0) rounded once.
-// Every output element is ONE accumulator chain per product in ascending (chunk, ci): no atomics, no split-K; equal calls give equal
-// bits and a sample's result does not depend on the batch around it.
-#include "common.h"
-
-#pragma clang fp contract(off)
+// One accumulator chain per product; equal calls give equal bits and a sample's result does not depend on the batch around it.
+#include "dense_tile.h"
 
 namespace bevamd {
 
-typedef float bt_f32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 bt_f16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bt_bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned int bt_u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int bt_u32x2 __attribute__((ext_vector_type(2)));
-
 constexpr int BT_PIX = 128;                   // flat output pixels of one workgroup
-constexpr int BT_CK = 32;                     // channels of one staged chunk = one MFMA k-step
-constexpr int BT_PSTR = BT_CK + 8;            // 16-bit elements per pixel in LDS (80 bytes: the padding spreads the banks)
 constexpr int BT_THREADS = 256;
-constexpr int BT_UNITS = BT_PIX * (BT_CK / 8);               // a unit: 8 channels of one pixel, 16 bytes
+constexpr int BT_UNITS = BT_PIX * (CK / 8);                  // a unit: 8 channels of one pixel, 16 bytes
 constexpr int BT_UPT = BT_UNITS / BT_THREADS;
 static_assert(BT_UNITS % BT_THREADS == 0, "every thread stages the same number of units");
 
@@ -60,52 +46,9 @@ struct BtArgs {
   int dst_nhwc;
 };
 
-template <bool BF16>
-__device__ __forceinline__ bt_f32x4 bt_mfma(bt_u32x4 a, bt_u32x4 b, bt_f32x4 acc) {
-  if constexpr (BF16)
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bt_bf16x8, a), __builtin_bit_cast(bt_bf16x8, b), acc, 0, 0, 0);
-  else
-    return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(bt_f16x8, a), __builtin_bit_cast(bt_f16x8, b), acc, 0, 0, 0);
-}
-
-template <bool BF16>
-__device__ __forceinline__ unsigned short bt_round(float v) {
-  if constexpr (BF16)
-    return __builtin_bit_cast(unsigned short, (__bf16)v);
-  else
-    return __builtin_bit_cast(unsigned short, (_Float16)v);
-}
-
-template <bool BF16>
-__device__ __forceinline__ float bt_widen(unsigned short v) {
-  if constexpr (BF16)
-    return (float)__builtin_bit_cast(__bf16, v);
-  else
-    return (float)__builtin_bit_cast(_Float16, v);
-}
-
-// 8 channels [c, c + 8) of one pixel as a 16-byte unit: `base` is the element offset of channel 0 of that pixel, `cstr` the stride
-// between channels (1: NHWC, one load; the map's size: NCHW, eight loads); the caller checked the bounds
-__device__ __forceinline__ bt_u32x4 bt_load_unit(const unsigned short* src, int nhwc, size_t base, size_t cstr, int c) {
-  bt_u32x4 v;
-  if (nhwc) {
-    v = *reinterpret_cast<const bt_u32x4*>(src + base + c);
-  } else {
-    const unsigned short* q = src + base + (size_t)c * cstr;
-    unsigned int e[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) e[j] = q[(size_t)j * cstr];
-    v[0] = e[0] | (e[1] << 16);
-    v[1] = e[2] | (e[3] << 16);
-    v[2] = e[4] | (e[5] << 16);
-    v[3] = e[6] | (e[7] << 16);
-  }
-  return v;
-}
-
 template <bool BF16, int MT, bool DS>
 __global__ __launch_bounds__(BT_THREADS) void bottleneck_tail_kernel(BtArgs a) {
-  __shared__ __attribute__((aligned(16))) unsigned short xs[BT_PIX * BT_PSTR];
+  __shared__ __attribute__((aligned(16))) unsigned short xs[BT_PIX * PSTR];
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int p0 = blockIdx.x * BT_PIX;
@@ -120,6 +63,7 @@ __global__ __launch_bounds__(BT_THREADS) void bottleneck_tail_kernel(BtArgs a) {
 #pragma unroll
   for (int u = 0; u < BT_UPT; ++u) {
     const int idx = tid + u * BT_THREADS;
+    // unit_of<BT_PIX>, written out: through the helper the identity kernels come out with two instructions exchanged
     if (a.h_nhwc) { ug_h[u] = idx & 3; up_h[u] = idx >> 2; } else { ug_h[u] = idx / BT_PIX; up_h[u] = idx - ug_h[u] * BT_PIX; }
     if (a.x_nhwc) { ug_x[u] = idx & 3; up_x[u] = idx >> 2; } else { ug_x[u] = idx / BT_PIX; up_x[u] = idx - ug_x[u] * BT_PIX; }
     {
@@ -138,49 +82,49 @@ __global__ __launch_bounds__(BT_THREADS) void bottleneck_tail_kernel(BtArgs a) {
     }
   }
 
-  bt_u32x4 pre[BT_UPT];
+  u32x4 pre[BT_UPT];
   auto load_h = [&](int ch) {
 #pragma unroll
     for (int u = 0; u < BT_UPT; ++u) {
-      const int c = ch * BT_CK + ug_h[u] * 8;
-      bt_u32x4 v = {0u, 0u, 0u, 0u};
-      if (live_h[u] && c < a.P) v = bt_load_unit(a.h, a.h_nhwc, base_h[u], (size_t)ohw, c);
+      const int c = ch * CK + ug_h[u] * 8;
+      u32x4 v = {0u, 0u, 0u, 0u};
+      if (live_h[u] && c < a.P) v = load_unit(a.h, a.h_nhwc, base_h[u], (size_t)ohw, c);
       pre[u] = v;
     }
   };
   auto store_h = [&]() {
 #pragma unroll
-    for (int u = 0; u < BT_UPT; ++u) *reinterpret_cast<bt_u32x4*>(xs + up_h[u] * BT_PSTR + ug_h[u] * 8) = pre[u];
+    for (int u = 0; u < BT_UPT; ++u) *reinterpret_cast<u32x4*>(xs + up_h[u] * PSTR + ug_h[u] * 8) = pre[u];
   };
   auto load_x = [&](int ch) {
 #pragma unroll
     for (int u = 0; u < BT_UPT; ++u) {
-      const int c = ch * BT_CK + ug_x[u] * 8;
-      bt_u32x4 v = {0u, 0u, 0u, 0u};
-      if (live_x[u] && c < a.Cx) v = bt_load_unit(a.x, a.x_nhwc, base_x[u], xhw, c);
+      const int c = ch * CK + ug_x[u] * 8;
+      u32x4 v = {0u, 0u, 0u, 0u};
+      if (live_x[u] && c < a.Cx) v = load_unit(a.x, a.x_nhwc, base_x[u], xhw, c);
       pre[u] = v;
     }
   };
   auto store_x = [&]() {
 #pragma unroll
-    for (int u = 0; u < BT_UPT; ++u) *reinterpret_cast<bt_u32x4*>(xs + up_x[u] * BT_PSTR + ug_x[u] * 8) = pre[u];
+    for (int u = 0; u < BT_UPT; ++u) *reinterpret_cast<u32x4*>(xs + up_x[u] * PSTR + ug_x[u] * 8) = pre[u];
   };
 
   const int mh = wave & 1, q0 = (wave >> 1) * 64;        // the wave's channel half and first pixel of the tile
   const int lr = lane & 15, lg = lane >> 4;
   const int mt0 = ctile * (2 * MT) + mh * MT;            // the wave's first tile of 16 channels
   // B fragment: lane holds S[k = 8 lg + j][pixel q0 + 16 n + lr]
-  const unsigned short* xb = xs + (q0 + lr) * BT_PSTR + lg * 8;
+  const unsigned short* xb = xs + (q0 + lr) * PSTR + lg * 8;
 
-  bt_f32x4 acc[MT][4];
+  f32x4 acc[MT][4];
 #pragma unroll
   for (int m = 0; m < MT; ++m)
 #pragma unroll
-    for (int n = 0; n < 4; ++n) acc[m][n] = bt_f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int n = 0; n < 4; ++n) acc[m][n] = f32x4{0.f, 0.f, 0.f, 0.f};
 
   {
     // A fragment of (channel tile mt, chunk): 64 lanes x 16 bytes
-    const bt_u32x4* wp = reinterpret_cast<const bt_u32x4*>(a.packed3) + ((size_t)mt0 * a.nch3) * 64 + lane;
+    const u32x4* wp = reinterpret_cast<const u32x4*>(a.packed3) + ((size_t)mt0 * a.nch3) * 64 + lane;
     const size_t wtile = (size_t)a.nch3 * 64;
     load_h(0);
 #pragma unroll 1
@@ -189,41 +133,25 @@ __global__ __launch_bounds__(BT_THREADS) void bottleneck_tail_kernel(BtArgs a) {
       __syncthreads();
       if (ch + 1 < a.nch3) load_h(ch + 1);
       else if constexpr (DS) load_x(0);
-      bt_u32x4 af[MT], bf[4];
-#pragma unroll
-      for (int m = 0; m < MT; ++m) af[m] = wp[(size_t)m * wtile + (size_t)ch * 64];
-#pragma unroll
-      for (int n = 0; n < 4; ++n) bf[n] = *reinterpret_cast<const bt_u32x4*>(xb + (n * 16) * BT_PSTR);
-#pragma unroll
-      for (int m = 0; m < MT; ++m)
-#pragma unroll
-        for (int n = 0; n < 4; ++n) acc[m][n] = bt_mfma<BF16>(af[m], bf[n], acc[m][n]);
+      chunk_mma<BF16, MT, 1, 1, 16>(acc, wp, wtile, ch, xb);
       __syncthreads();   // the next chunk overwrites the tile
     }
   }
 
-  bt_f32x4 accd[DS ? MT : 1][4];
+  f32x4 accd[DS ? MT : 1][4];
   if constexpr (DS) {
 #pragma unroll
     for (int m = 0; m < MT; ++m)
 #pragma unroll
-      for (int n = 0; n < 4; ++n) accd[m][n] = bt_f32x4{0.f, 0.f, 0.f, 0.f};
-    const bt_u32x4* wp = reinterpret_cast<const bt_u32x4*>(a.packed_d) + ((size_t)mt0 * a.nchd) * 64 + lane;
+      for (int n = 0; n < 4; ++n) accd[m][n] = f32x4{0.f, 0.f, 0.f, 0.f};
+    const u32x4* wp = reinterpret_cast<const u32x4*>(a.packed_d) + ((size_t)mt0 * a.nchd) * 64 + lane;
     const size_t wtile = (size_t)a.nchd * 64;
 #pragma unroll 1
     for (int ch = 0; ch < a.nchd; ++ch) {
       store_x();
       __syncthreads();
       if (ch + 1 < a.nchd) load_x(ch + 1);
-      bt_u32x4 af[MT], bf[4];
-#pragma unroll
-      for (int m = 0; m < MT; ++m) af[m] = wp[(size_t)m * wtile + (size_t)ch * 64];
-#pragma unroll
-      for (int n = 0; n < 4; ++n) bf[n] = *reinterpret_cast<const bt_u32x4*>(xb + (n * 16) * BT_PSTR);
-#pragma unroll
-      for (int m = 0; m < MT; ++m)
-#pragma unroll
-        for (int n = 0; n < 4; ++n) accd[m][n] = bt_mfma<BF16>(af[m], bf[n], accd[m][n]);
+      chunk_mma<BF16, MT, 1, 1, 16>(accd, wp, wtile, ch, xb);
       __syncthreads();
     }
   }
@@ -237,42 +165,27 @@ __global__ __launch_bounds__(BT_THREADS) void bottleneck_tail_kernel(BtArgs a) {
 #pragma unroll
     for (int m = 0; m < MT; ++m) {
       const int co = (mt0 + m) * 16 + lg * 4;
-      const float4 sc = *reinterpret_cast<const float4*>(a.scale3 + co);
-      const float4 sh = *reinterpret_cast<const float4*>(a.shift3 + co);
-      const float s4[4] = {sc.x, sc.y, sc.z, sc.w}, t4[4] = {sh.x, sh.y, sh.z, sh.w};
+      const Affine4 bn3 = load_affine4(a.scale3, a.shift3, co);
       float res[4];
       if constexpr (DS) {
-        const float4 scd = *reinterpret_cast<const float4*>(a.scale_d + co);
-        const float4 shd = *reinterpret_cast<const float4*>(a.shift_d + co);
-        const float sd4[4] = {scd.x, scd.y, scd.z, scd.w}, td4[4] = {shd.x, shd.y, shd.z, shd.w};
+        const Affine4 bnd = load_affine4(a.scale_d, a.shift_d, co);
 #pragma unroll
-        for (int q = 0; q < 4; ++q) res[q] = fmaf(accd[m][n][q], sd4[q], td4[q]);
+        for (int q = 0; q < 4; ++q) res[q] = affine(accd[m][n][q], bnd, q);
       } else {
         // identity: x is [B, C, OH, OW]
         if (a.x_nhwc) {
-          const bt_u32x2 w = *reinterpret_cast<const bt_u32x2*>(a.x + (size_t)p * a.C + co);
-          res[0] = bt_widen<BF16>((unsigned short)(w[0] & 0xffffu));
-          res[1] = bt_widen<BF16>((unsigned short)(w[0] >> 16));
-          res[2] = bt_widen<BF16>((unsigned short)(w[1] & 0xffffu));
-          res[3] = bt_widen<BF16>((unsigned short)(w[1] >> 16));
+          widen4<BF16>(*reinterpret_cast<const u32x2*>(a.x + (size_t)p * a.C + co), res);
         } else {
           const unsigned short* r0 = a.x + ((size_t)b * a.C + co) * ohw + rem;
 #pragma unroll
-          for (int q = 0; q < 4; ++q) res[q] = bt_widen<BF16>(r0[(size_t)q * ohw]);
+          for (int q = 0; q < 4; ++q) res[q] = widen16<BF16>(r0[(size_t)q * ohw]);
         }
       }
       unsigned short r[4];
 #pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const float v = fmaf(acc[m][n][q], s4[q], t4[q]);
-        const float y = v + res[q];
-        r[q] = bt_round<BF16>(y > 0.f ? y : 0.f);
-      }
+      for (int q = 0; q < 4; ++q) r[q] = round16<BF16>(relu(affine(acc[m][n][q], bn3, q) + res[q]));
       if (a.dst_nhwc) {
-        bt_u32x2 o;
-        o[0] = (unsigned int)r[0] | ((unsigned int)r[1] << 16);
-        o[1] = (unsigned int)r[2] | ((unsigned int)r[3] << 16);
-        *reinterpret_cast<bt_u32x2*>(a.dst + (size_t)p * a.C + co) = o;
+        *reinterpret_cast<u32x2*>(a.dst + (size_t)p * a.C + co) = pack4(r[0], r[1], r[2], r[3]);
       } else {
         unsigned short* d = a.dst + ((size_t)b * a.C + co) * ohw + rem;
 #pragma unroll
@@ -291,11 +204,6 @@ static void bt_launch(const BtArgs& a, hipStream_t stream) {
     bottleneck_tail_kernel<BF16, 2, DS><<<dim3(tiles, a.C / 64), dim3(BT_THREADS), 0, stream>>>(a);
   else
     bottleneck_tail_kernel<BF16, 1, DS><<<dim3(tiles, a.C / 32), dim3(BT_THREADS), 0, stream>>>(a);
-}
-
-static bool bt_overlap(const void* p, long long pbytes, const void* q, long long qbytes) {
-  const uintptr_t a = (uintptr_t)p, b = (uintptr_t)q;
-  return a < b + (uintptr_t)qbytes && b < a + (uintptr_t)pbytes;
 }
 
 }  // namespace bevamd
@@ -346,10 +254,10 @@ int bevamd_bottleneck_tail_forward(const void* h, int h_layout, int planes, cons
                    "bottleneck_tail_forward: the identity residual needs x [%d, %d, %d] equal to the output [%d, %d, %d] at stride 1, got stride %d",
                    x_channels, x_height, x_width, channels, out_height, out_width, stride);
   }
-  const int nch3 = (planes + BT_CK - 1) / BT_CK, nchd = ds ? (x_channels + BT_CK - 1) / BT_CK : 0;
-  const long long want3 = (long long)channels * nch3 * BT_CK;
+  const int nch3 = (planes + CK - 1) / CK, nchd = ds ? (x_channels + CK - 1) / CK : 0;
+  const long long want3 = (long long)channels * nch3 * CK;
   BEVAMD_REQUIRE(packed3_elems == want3, "bottleneck_tail_forward: packed3 holds %lld elements, this block needs %lld", packed3_elems, want3);
-  const long long wantd = (long long)channels * nchd * BT_CK;
+  const long long wantd = (long long)channels * nchd * CK;
   BEVAMD_REQUIRE(packed_d_elems == wantd, "bottleneck_tail_forward: packed_d holds %lld elements, this block needs %lld", packed_d_elems, wantd);
   const long long npix = (long long)batch * out_height * (long long)out_width;
   const long long want_dst = npix * channels;
@@ -373,7 +281,7 @@ int bevamd_bottleneck_tail_forward(const void* h, int h_layout, int planes, cons
   BEVAMD_REQUIRE(dst_layout == 0 || ((uintptr_t)dst & 7) == 0, "bottleneck_tail_forward: an NHWC dst is not 8-byte aligned");
   const long long h_bytes = 2LL * npix * planes;
   const long long x_bytes = 2LL * batch * x_channels * x_height * (long long)x_width;
-  BEVAMD_REQUIRE(!bt_overlap(dst, 2 * want_dst, h, h_bytes) && !bt_overlap(dst, 2 * want_dst, x, x_bytes),
+  BEVAMD_REQUIRE(!ranges_overlap(dst, 2 * want_dst, h, h_bytes) && !ranges_overlap(dst, 2 * want_dst, x, x_bytes),
                  "bottleneck_tail_forward: dst overlaps h or x");
 
   BtArgs a;

@@ -6,10 +6,9 @@
 //   mmdet3d/models/necks/lss.py:54-64              LSSFPN.forward: F.interpolate + torch.cat + Conv2d 1x1 + BatchNorm2d + ReLU;
 //                                                  nn.Upsample + Conv2d 3x3 + BatchNorm2d + ReLU
 //
-// Native formulation: the implicit GEMM of bev_conv.hip (stride 1, kernel 1 or 3) on v_mfma_f32_16x16x32_{f16,bf16}: four waves own
-// 8 x 16 output pixels x 32 * MT output channels, the haloed input tile is staged in LDS in chunks of 32 channels as
-// [pixel][32 + 8], the next chunk is loaded into registers while the current one is multiplied, the weights stream from L2 in
-// A-fragment order, and the epilogue is y = fma(acc, scale, shift) (ReLU optional) rounded once into a channel window of dst.
+// Native formulation: the dense conv tile of dense_tile.h at stride 1, kernel 1 or 3: four waves own 8 x 16 output pixels x
+// 32 * MT output channels, the next chunk is loaded into registers while the current one is multiplied, and the epilogue is
+// y = fma(acc, scale, shift) (ReLU optional) rounded once into a channel window of dst.
 // What is new is the staging: each of the two sources has its OWN map and layout.  A source whose map equals the output map is
 // copied (no arithmetic).  Any other source is resampled while its unit (8 channels of one staged pixel) is built: the four
 // neighbours are loaded (four 16-byte loads from an NHWC source, 4 x 8 two-byte loads from an NCHW one), kept in registers while the
@@ -18,24 +17,13 @@
 // rounded ONCE to the storage type and written as one 16-byte LDS store.  y0, y1, ly of the tile's rows and x0, x1, lx of its
 // columns do not depend on the chunk: they are computed once per workgroup into small LDS tables.  The zero padding of a 3 x 3
 // layer applies to the RESAMPLED map.  y1 = y0 + (y0 < h - 1) and x1 alike: no address outside a source is formed.
-// Every output element is ONE accumulator chain in ascending (chunk, tap, ci) whatever MT is: no atomics, no split-K, no workspace;
-// equal calls give equal bits and a sample's result does not depend on the batch around it (MT is chosen from the grid size, and
+// Equal calls give equal bits and a sample's result does not depend on the batch around it (MT is chosen from the grid size, and
 // the bits do not depend on MT).
-#include "common.h"
-
-#pragma clang fp contract(off)
+#include "dense_tile.h"
 
 namespace bevamd {
 
-typedef float nk_f32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 nk_f16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 nk_bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned int nk_u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int nk_u32x2 __attribute__((ext_vector_type(2)));
-
 constexpr int NK_TH = 8, NK_TW = 16;          // output pixels of one workgroup
-constexpr int NK_CK = 32;                     // channels of one staged chunk = one MFMA k-step per tap
-constexpr int NK_PSTR = NK_CK + 8;            // 16-bit elements per pixel in LDS (80 bytes: the padding spreads the banks)
 constexpr int NK_THREADS = 256;
 constexpr int NK_FILL = 256;                  // workgroups wanted before a wider channel tile is taken (compute units of the chip)
 
@@ -56,46 +44,11 @@ struct NkArgs {
   int dst_c, dst_off, dst_nhwc;
 };
 
-template <bool BF16>
-__device__ __forceinline__ nk_f32x4 nk_mfma(nk_u32x4 a, nk_u32x4 b, nk_f32x4 acc) {
-  if constexpr (BF16)
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(nk_bf16x8, a), __builtin_bit_cast(nk_bf16x8, b), acc, 0, 0, 0);
-  else
-    return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(nk_f16x8, a), __builtin_bit_cast(nk_f16x8, b), acc, 0, 0, 0);
-}
-
-template <bool BF16>
-__device__ __forceinline__ unsigned short nk_round(float v) {
-  if constexpr (BF16)
-    return __builtin_bit_cast(unsigned short, (__bf16)v);
-  else
-    return __builtin_bit_cast(unsigned short, (_Float16)v);
-}
-
-template <bool BF16>
-__device__ __forceinline__ float nk_float(unsigned int bits16) {
-  if constexpr (BF16)
-    return __builtin_bit_cast(float, bits16 << 16);
-  else
-    return (float)__builtin_bit_cast(_Float16, (unsigned short)bits16);
-}
-
-// 8 channels [cc, cc + 8) of the pixel at offset `off` (= y * w + x) of sample b: one 16-byte load (NHWC) or eight 2-byte loads
-__device__ __forceinline__ nk_u32x4 nk_load8(const unsigned short* src, int nhwc, int b, int cs, int cc, size_t hw, int off) {
-  nk_u32x4 v;
-  if (nhwc) {
-    v = *reinterpret_cast<const nk_u32x4*>(src + ((size_t)b * hw + off) * cs + cc);
-  } else {
-    const unsigned short* q = src + ((size_t)b * cs + cc) * hw + off;
-    unsigned int e[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) e[j] = q[(size_t)j * hw];
-    v[0] = e[0] | (e[1] << 16);
-    v[1] = e[2] | (e[3] << 16);
-    v[2] = e[4] | (e[5] << 16);
-    v[3] = e[6] | (e[7] << 16);
-  }
-  return v;
+// 8 channels [cc, cc + 8) of the pixel at offset `off` (= y * w + x) of sample b: one 16-byte load (NHWC) or eight 2-byte loads.
+// Its own address arithmetic, not load_unit's base + c * cstr: that form adds up to 173 instructions a kernel (profiles/EXPERIMENTS.md)
+__device__ __forceinline__ u32x4 nk_load8(const unsigned short* src, int nhwc, int b, int cs, int cc, size_t hw, int off) {
+  if (nhwc) return *reinterpret_cast<const u32x4*>(src + ((size_t)b * hw + off) * cs + cc);
+  return gather8(src + ((size_t)b * cs + cc) * hw + off, hw);
 }
 
 // RS: at least one source is resampled (four neighbours per unit are held in registers); without it the staging is a copy
@@ -103,10 +56,10 @@ template <bool BF16, int MT, int KS, bool RS>
 __global__ __launch_bounds__(NK_THREADS) void cam_neck_conv_kernel(NkArgs a) {
   constexpr int P = KS / 2, TAPS = KS * KS;
   constexpr int IH = NK_TH - 1 + KS, IW = NK_TW - 1 + KS;               // the haloed input tile
-  constexpr int NPIX = IH * IW, UNITS = NPIX * (NK_CK / 8);             // a unit: 8 channels of one pixel, 16 bytes
+  constexpr int NPIX = IH * IW, UNITS = NPIX * (CK / 8);             // a unit: 8 channels of one pixel, 16 bytes
   constexpr int UPT = (UNITS + NK_THREADS - 1) / NK_THREADS;
   constexpr int NB = RS ? 4 : 1;                                        // 16-byte registers per unit
-  __shared__ __attribute__((aligned(16))) unsigned short xs[NPIX * NK_PSTR];
+  __shared__ __attribute__((aligned(16))) unsigned short xs[NPIX * PSTR];
   __shared__ int t_y0[2][IH], t_y1[2][IH], t_x0[2][IW], t_x1[2][IW];    // per source: row offsets y * w, columns x
   __shared__ float t_ly[2][IH], t_lx[2][IW];
 
@@ -148,10 +101,11 @@ __global__ __launch_bounds__(NK_THREADS) void cam_neck_conv_kernel(NkArgs a) {
     __syncthreads();
   }
 
-  nk_u32x4 pre[UPT][NB];
-  // the unit -> (pixel, channel group) map of a chunk follows the layout of the source its first channel lies in
+  u32x4 pre[UPT][NB];
+  // the unit -> (pixel, channel group) map of a chunk follows the layout of the source its first channel lies in (unit_of written
+  // out: through the helper the selects of the 1 x 1 kernels come out in another order)
   auto unit = [&](int ch, int idx, int& p, int& grp) {
-    const int nh = ch * NK_CK < a.c0 ? a.nhwc0 : a.nhwc1;
+    const int nh = ch * CK < a.c0 ? a.nhwc0 : a.nhwc1;
     if (nh) { grp = idx & 3; p = idx >> 2; } else { grp = idx / NPIX; p = idx - grp * NPIX; }
   };
   auto load_chunk = [&](int ch) {
@@ -159,13 +113,13 @@ __global__ __launch_bounds__(NK_THREADS) void cam_neck_conv_kernel(NkArgs a) {
     for (int u = 0; u < UPT; ++u) {
       const int idx = tid + u * NK_THREADS;
 #pragma unroll
-      for (int q = 0; q < NB; ++q) pre[u][q] = nk_u32x4{0u, 0u, 0u, 0u};
+      for (int q = 0; q < NB; ++q) pre[u][q] = u32x4{0u, 0u, 0u, 0u};
       if (idx < UNITS) {
         int p, grp;
         unit(ch, idx, p, grp);
         const int iy = p / IW, ix = p - iy * IW;
         const int gy = iy0 + iy, gx = ix0 + ix;
-        const int c = ch * NK_CK + grp * 8;
+        const int c = ch * CK + grp * 8;
         if (gy >= 0 && gy < a.OH && gx >= 0 && gx < a.OW && c < ctot) {
           const bool first = c < a.c0;
           const unsigned short* src = first ? a.src0 : a.src1;
@@ -199,9 +153,9 @@ __global__ __launch_bounds__(NK_THREADS) void cam_neck_conv_kernel(NkArgs a) {
       if (idx < UNITS) {
         int p, grp;
         unit(ch, idx, p, grp);
-        nk_u32x4 v = pre[u][0];
+        u32x4 v = pre[u][0];
         if constexpr (RS) {
-          const int c = ch * NK_CK + grp * 8;
+          const int c = ch * CK + grp * 8;
           const bool first = c < a.c0;
           if (first ? a.rs0 : a.rs1) {                   // a unit that was not loaded is four zeros and stays zero
             const int iy = p / IW, ix = p - iy * IW, s = first ? 0 : 1;
@@ -211,10 +165,10 @@ __global__ __launch_bounds__(NK_THREADS) void cam_neck_conv_kernel(NkArgs a) {
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
               const int wd = j >> 1, sh = (j & 1) * 16;
-              const float a00 = nk_float<BF16>((pre[u][0][wd] >> sh) & 0xffffu), a01 = nk_float<BF16>((pre[u][1][wd] >> sh) & 0xffffu);
-              const float a10 = nk_float<BF16>((pre[u][2][wd] >> sh) & 0xffffu), a11 = nk_float<BF16>((pre[u][3][wd] >> sh) & 0xffffu);
+              const float a00 = widen16<BF16>((unsigned short)(pre[u][0][wd] >> sh)), a01 = widen16<BF16>((unsigned short)(pre[u][1][wd] >> sh));
+              const float a10 = widen16<BF16>((unsigned short)(pre[u][2][wd] >> sh)), a11 = widen16<BF16>((unsigned short)(pre[u][3][wd] >> sh));
               const float top = hx * a00 + lx * a01, bot = hx * a10 + lx * a11;
-              r[j] = nk_round<BF16>(hy * top + ly * bot);
+              r[j] = round16<BF16>(hy * top + ly * bot);
             }
             v[0] = r[0] | (r[1] << 16);
             v[1] = r[2] | (r[3] << 16);
@@ -222,7 +176,7 @@ __global__ __launch_bounds__(NK_THREADS) void cam_neck_conv_kernel(NkArgs a) {
             v[3] = r[6] | (r[7] << 16);
           }
         }
-        *reinterpret_cast<nk_u32x4*>(xs + p * NK_PSTR + grp * 8) = v;
+        *reinterpret_cast<u32x4*>(xs + p * PSTR + grp * 8) = v;
       }
     }
   };
@@ -231,16 +185,16 @@ __global__ __launch_bounds__(NK_THREADS) void cam_neck_conv_kernel(NkArgs a) {
   const int lr = lane & 15, lg = lane >> 4;
   const int mt0 = ctile * (2 * MT) + mh * MT;            // the wave's first tile of 16 channels
   // A fragment of (channel tile mt, chunk, tap): 64 lanes x 16 bytes
-  const nk_u32x4* wp = reinterpret_cast<const nk_u32x4*>(a.packed) + ((size_t)mt0 * a.nch) * (TAPS * 64) + lane;
+  const u32x4* wp = reinterpret_cast<const u32x4*>(a.packed) + ((size_t)mt0 * a.nch) * (TAPS * 64) + lane;
   const size_t wtile = (size_t)a.nch * (TAPS * 64);
   // B fragment: lane holds X[k = 8 lg + j][pixel lr] of pixel row r0 + n
-  const unsigned short* xb = xs + (r0 * IW + lr) * NK_PSTR + lg * 8;
+  const unsigned short* xb = xs + (r0 * IW + lr) * PSTR + lg * 8;
 
-  nk_f32x4 acc[MT][4];
+  f32x4 acc[MT][4];
 #pragma unroll
   for (int m = 0; m < MT; ++m)
 #pragma unroll
-    for (int n = 0; n < 4; ++n) acc[m][n] = nk_f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int n = 0; n < 4; ++n) acc[m][n] = f32x4{0.f, 0.f, 0.f, 0.f};
 
   load_chunk(0);
 #pragma unroll 1
@@ -248,19 +202,7 @@ __global__ __launch_bounds__(NK_THREADS) void cam_neck_conv_kernel(NkArgs a) {
     store_chunk(ch);
     __syncthreads();
     if (ch + 1 < a.nch) load_chunk(ch + 1);
-#pragma unroll
-    for (int tap = 0; tap < TAPS; ++tap) {
-      const int ky = tap / KS, kx = tap % KS;
-      nk_u32x4 af[MT], bf[4];
-#pragma unroll
-      for (int m = 0; m < MT; ++m) af[m] = wp[(size_t)m * wtile + (size_t)(ch * TAPS + tap) * 64];
-#pragma unroll
-      for (int n = 0; n < 4; ++n) bf[n] = *reinterpret_cast<const nk_u32x4*>(xb + ((n + ky) * IW + kx) * NK_PSTR);
-#pragma unroll
-      for (int m = 0; m < MT; ++m)
-#pragma unroll
-        for (int n = 0; n < 4; ++n) acc[m][n] = nk_mfma<BF16>(af[m], bf[n], acc[m][n]);
-    }
+    chunk_mma<BF16, MT, KS, 1, IW>(acc, wp, wtile, ch, xb);
     __syncthreads();   // the next chunk overwrites the tile
   }
 
@@ -269,9 +211,7 @@ __global__ __launch_bounds__(NK_THREADS) void cam_neck_conv_kernel(NkArgs a) {
 #pragma unroll
   for (int m = 0; m < MT; ++m) {
     const int co = (mt0 + m) * 16 + lg * 4;
-    const float4 sc = *reinterpret_cast<const float4*>(a.scale + co);
-    const float4 sh = *reinterpret_cast<const float4*>(a.shift + co);
-    const float s4[4] = {sc.x, sc.y, sc.z, sc.w}, t4[4] = {sh.x, sh.y, sh.z, sh.w};
+    const Affine4 bn = load_affine4(a.scale, a.shift, co);
 #pragma unroll
     for (int n = 0; n < 4; ++n) {
       const int oy = oy0 + r0 + n;
@@ -279,17 +219,11 @@ __global__ __launch_bounds__(NK_THREADS) void cam_neck_conv_kernel(NkArgs a) {
       unsigned short r[4];
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
-        float v = fmaf(acc[m][n][q], s4[q], t4[q]);
-        // y is round16 of the fp32 value, as bev_conv.hip computes it: without this the compiler fuses the fma and the conversion
-        // to fp16 into v_fma_mixlo_f16, which was seen to differ from that in about one element in 2^13
-        asm("" : "+v"(v));
-        r[q] = nk_round<BF16>(a.relu ? (v > 0.f ? v : 0.f) : v);
+        const float v = affine<true>(acc[m][n][q], bn, q);
+        r[q] = round16<BF16>(a.relu ? relu(v) : v);
       }
       if (a.dst_nhwc) {
-        nk_u32x2 o;
-        o[0] = (unsigned int)r[0] | ((unsigned int)r[1] << 16);
-        o[1] = (unsigned int)r[2] | ((unsigned int)r[3] << 16);
-        *reinterpret_cast<nk_u32x2*>(a.dst + (((size_t)b * a.OH + oy) * a.OW + ox) * a.dst_c + a.dst_off + co) = o;
+        *reinterpret_cast<u32x2*>(a.dst + (((size_t)b * a.OH + oy) * a.OW + ox) * a.dst_c + a.dst_off + co) = pack4(r[0], r[1], r[2], r[3]);
       } else {
         unsigned short* d = a.dst + (((size_t)b * a.dst_c + a.dst_off + co) * a.OH + oy) * a.OW + ox;
 #pragma unroll
@@ -364,8 +298,8 @@ int bevamd_neck_conv_forward(const void* src0, int channels0, int height0, int w
                  out_channels, dst_channels_total);
   BEVAMD_REQUIRE((long long)height0 * width0 <= 0x7fffffffLL && (!two || (long long)height1 * width1 <= 0x7fffffffLL),
                  "neck_conv_forward: a source map has more than 2^31 - 1 pixels");
-  const int nch = (int)(((long long)channels0 + channels1 + NK_CK - 1) / NK_CK);
-  const long long want_packed = (long long)out_channels * nch * kernel * kernel * NK_CK;
+  const int nch = (int)(((long long)channels0 + channels1 + CK - 1) / CK);
+  const long long want_packed = (long long)out_channels * nch * kernel * kernel * CK;
   BEVAMD_REQUIRE(packed_elems == want_packed, "neck_conv_forward: packed holds %lld elements, this layer needs %lld", packed_elems, want_packed);
   const long long want_dst = (long long)batch * dst_channels_total * out_height * (long long)out_width;
   BEVAMD_REQUIRE(dst_elems == want_dst, "neck_conv_forward: dst holds %lld elements, [%d, %d, %d, %d] needs %lld", dst_elems, batch,

@@ -6,16 +6,14 @@
 //   mmdet3d/models/vtransforms/depth_lss.py:88-97      the end of depthnet: Conv2d(Cin, D + C, 1), softmax over D, the split
 //   mmdet3d/models/vtransforms/lss.py:63-75            the same end of LSSTransform's one-layer depthnet
 //
-// Native formulation: implicit GEMMs D[channel][pixel] on v_mfma_f32_16x16x32_{f16,bf16} with fp32 accumulation, the operand
-// layouts of bev_conv.hip (A: packed weights, one 16-byte load per lane; B: 8 channels of one pixel, one 16-byte read per lane;
-// D: pixel on the lane, channel = 16 tile + 4 (lane >> 4) + reg).
+// Native formulation: implicit GEMMs D[channel][pixel] with the operand layouts of dense_tile.h.
 //   * stem, launch 1 (layers 1 + 2): a workgroup of four waves owns 8 x 16 layer-2 pixels x 32 channels.  The 33 x 65 depth tile is
 //     read once; layer 1 is a per-pixel function of the scalar depth, a1[c] = max(fma(d, s1[c], t1[c]), 0), computed in fp32 while
 //     staging, rounded once and kept in LDS as [pixel][8 channels] (16 bytes); a cell outside the image holds ZERO (layer 2 pads
 //     the output of layer 1, not the depth).  K = 25 taps x 8 channels = 200, padded to 224: k-step c of lane group g is tap 4 c + g,
 //     so a lane's B fragment is one 16-byte LDS read; the taps 25 .. 27 are zero on both operands.
 //   * stem, launch 2 (layer 3): 8 x 16 output pixels x 64 channels per workgroup from the 19 x 35 x 32 haloed tile of the layer-2
-//     map in LDS ([pixel][32 + 8 of padding]); K = 25 taps x 32 channels, one k-step per tap.
+//     map, staged as ONE chunk of the dense conv tile; K = 25 taps x 32 channels, one k-step per tap.
 //   * both epilogues: y = max(fma(acc, scale[co], shift[co]), 0) in fp32, rounded once, 8-byte NHWC stores of 4 channels.
 //   * head: a wave owns 32 pixels (two MFMA column tiles) and ALL D + C rows (up to 16 tiles of 16: 128 accumulator registers).
 //     The B fragments come straight from the NHWC input (every element is read once), the A fragments stream from L2; no LDS, no
@@ -25,17 +23,9 @@
 //     depth = exp(z - max) / sum with ocml's expf and an IEEE division.
 // Every output element is ONE accumulator chain in a fixed order: no atomics, no split-K; equal calls give equal bits and a
 // sample's result does not depend on the batch around it.  No address outside the tensors is formed.
-#include "common.h"
-
-#pragma clang fp contract(off)
+#include "dense_tile.h"
 
 namespace bevamd {
-
-typedef float cn_f32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 cn_f16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 cn_bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned int cn_u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int cn_u32x2 __attribute__((ext_vector_type(2)));
 
 constexpr int CN_TH = 8, CN_TW = 16;                 // output pixels of one workgroup (both stem launches)
 constexpr int CN_THREADS = 256;
@@ -45,42 +35,17 @@ constexpr int CN_S2_IH = (CN_TH - 1) * 4 + CN_K5, CN_S2_IW = (CN_TW - 1) * 4 + C
 constexpr int CN_S2_STEPS = 7;                       // ceil(200 / 32)
 // launch 2: the layer-2 tile of an 8 x 16 layer-3 tile at stride 2
 constexpr int CN_S3_IH = (CN_TH - 1) * 2 + CN_K5, CN_S3_IW = (CN_TW - 1) * 2 + CN_K5;      // 19 x 35
-constexpr int CN_S3_PSTR = 32 + 8;                   // 16-bit elements per pixel in LDS (80 bytes: the padding spreads the banks)
 constexpr int CN_HEAD_NT = 2;                        // MFMA column tiles (16 pixels) of one wave of the head
 constexpr int CN_HEAD_PIX = 16 * CN_HEAD_NT;
 
-template <bool BF16>
-__device__ __forceinline__ cn_f32x4 cn_mfma(cn_u32x4 a, cn_u32x4 b, cn_f32x4 acc) {
-  if constexpr (BF16)
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(cn_bf16x8, a), __builtin_bit_cast(cn_bf16x8, b), acc, 0, 0, 0);
-  else
-    return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(cn_f16x8, a), __builtin_bit_cast(cn_f16x8, b), acc, 0, 0, 0);
-}
-
-template <bool BF16>
-__device__ __forceinline__ unsigned int cn_round(float v) {
-  if constexpr (BF16)
-    return __builtin_bit_cast(unsigned short, (__bf16)v);
-  else
-    return __builtin_bit_cast(unsigned short, (_Float16)v);
-}
-
 // y = round16(max(fma(acc, scale, shift), 0)) of the four channels co .. co + 3 of one pixel, one 8-byte store
 template <bool BF16>
-__device__ __forceinline__ void cn_store4(unsigned short* dst, cn_f32x4 acc, const float* scale, const float* shift, int co) {
-  const float4 sc = *reinterpret_cast<const float4*>(scale + co);
-  const float4 sh = *reinterpret_cast<const float4*>(shift + co);
-  const float s4[4] = {sc.x, sc.y, sc.z, sc.w}, t4[4] = {sh.x, sh.y, sh.z, sh.w};
+__device__ __forceinline__ void cn_store4(unsigned short* dst, f32x4 acc, const float* scale, const float* shift, int co) {
+  const Affine4 bn = load_affine4(scale, shift, co);
   unsigned int r[4];
 #pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    const float v = fmaf(acc[q], s4[q], t4[q]);
-    r[q] = cn_round<BF16>(v > 0.f ? v : 0.f);
-  }
-  cn_u32x2 o;
-  o[0] = r[0] | (r[1] << 16);
-  o[1] = r[2] | (r[3] << 16);
-  *reinterpret_cast<cn_u32x2*>(dst + co) = o;
+  for (int q = 0; q < 4; ++q) r[q] = round16<BF16>(relu(affine(acc[q], bn, q)));
+  *reinterpret_cast<u32x2*>(dst + co) = pack4(r[0], r[1], r[2], r[3]);
 }
 
 struct CnStemArgs {
@@ -121,32 +86,32 @@ __global__ __launch_bounds__(CN_THREADS) void cam_stem12_kernel(CnStemArgs a) {
   for (int p = tid; p < NPIX; p += CN_THREADS) {
     const int iy = p / CN_S2_IW, ix = p - iy * CN_S2_IW;
     const int gy = iy0 + iy, gx = ix0 + ix;
-    cn_u32x4 v = {0u, 0u, 0u, 0u};
+    u32x4 v = {0u, 0u, 0u, 0u};
     if (gy >= 0 && gy < a.H && gx >= 0 && gx < a.W) {
       const float d = img[(size_t)gy * a.W + gx];
       unsigned int r[8];
 #pragma unroll
       for (int c = 0; c < 8; ++c) {
         const float y = fmaf(d, s1[c], t1[c]);
-        r[c] = cn_round<BF16>(y > 0.f ? y : 0.f);
+        r[c] = round16<BF16>(y > 0.f ? y : 0.f);
       }
       v[0] = r[0] | (r[1] << 16);
       v[1] = r[2] | (r[3] << 16);
       v[2] = r[4] | (r[5] << 16);
       v[3] = r[6] | (r[7] << 16);
     }
-    *reinterpret_cast<cn_u32x4*>(xs + p * 8) = v;
+    *reinterpret_cast<u32x4*>(xs + p * 8) = v;
   }
   __syncthreads();
 
   const int lr = lane & 15, lg = lane >> 4;
   const int r0 = wave * 2;                                    // the wave's two pixel rows
-  const cn_u32x4* wp = reinterpret_cast<const cn_u32x4*>(a.packed2) + lane;
-  cn_f32x4 acc[2][2];
+  const u32x4* wp = reinterpret_cast<const u32x4*>(a.packed2) + lane;
+  f32x4 acc[2][2];
 #pragma unroll
   for (int m = 0; m < 2; ++m)
 #pragma unroll
-    for (int n = 0; n < 2; ++n) acc[m][n] = cn_f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int n = 0; n < 2; ++n) acc[m][n] = f32x4{0.f, 0.f, 0.f, 0.f};
 
 #pragma unroll
   for (int c = 0; c < CN_S2_STEPS; ++c) {
@@ -154,18 +119,18 @@ __global__ __launch_bounds__(CN_THREADS) void cam_stem12_kernel(CnStemArgs a) {
     const bool live = tap < CN_TAPS;
     const int tp = live ? tap : CN_TAPS - 1;
     const int ky = tp / CN_K5, kx = tp - ky * CN_K5;
-    cn_u32x4 af[2], bf[2];
+    u32x4 af[2], bf[2];
 #pragma unroll
     for (int m = 0; m < 2; ++m) af[m] = wp[(m * CN_S2_STEPS + c) * 64];
 #pragma unroll
     for (int n = 0; n < 2; ++n) {
-      const cn_u32x4 v = *reinterpret_cast<const cn_u32x4*>(xs + (((r0 + n) * 4 + ky) * CN_S2_IW + lr * 4 + kx) * 8);
-      bf[n] = live ? v : cn_u32x4{0u, 0u, 0u, 0u};
+      const u32x4 v = *reinterpret_cast<const u32x4*>(xs + (((r0 + n) * 4 + ky) * CN_S2_IW + lr * 4 + kx) * 8);
+      bf[n] = live ? v : u32x4{0u, 0u, 0u, 0u};
     }
 #pragma unroll
     for (int m = 0; m < 2; ++m)
 #pragma unroll
-      for (int n = 0; n < 2; ++n) acc[m][n] = cn_mfma<BF16>(af[m], bf[n], acc[m][n]);
+      for (int n = 0; n < 2; ++n) acc[m][n] = mfma16<BF16>(af[m], bf[n], acc[m][n]);
   }
 
   const int ox = ox0 + lr;
@@ -183,7 +148,7 @@ __global__ __launch_bounds__(CN_THREADS) void cam_stem12_kernel(CnStemArgs a) {
 template <bool BF16>
 __global__ __launch_bounds__(CN_THREADS) void cam_stem3_kernel(CnStemArgs a) {
   constexpr int NPIX = CN_S3_IH * CN_S3_IW, UNITS = NPIX * 4;                    // a unit: 8 channels of one pixel, 16 bytes
-  __shared__ __attribute__((aligned(16))) unsigned short xs[NPIX * CN_S3_PSTR];
+  __shared__ __attribute__((aligned(16))) unsigned short xs[NPIX * PSTR];
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int ty = blockIdx.x / a.tiles_x, tx = blockIdx.x - ty * a.tiles_x;
@@ -195,36 +160,24 @@ __global__ __launch_bounds__(CN_THREADS) void cam_stem3_kernel(CnStemArgs a) {
     const int grp = idx & 3, p = idx >> 2;
     const int iy = p / CN_S3_IW, ix = p - iy * CN_S3_IW;
     const int gy = iy0 + iy, gx = ix0 + ix;
-    cn_u32x4 v = {0u, 0u, 0u, 0u};
+    u32x4 v = {0u, 0u, 0u, 0u};
     if (gy >= 0 && gy < a.OH2 && gx >= 0 && gx < a.OW2)
-      v = *reinterpret_cast<const cn_u32x4*>(a.mid + (((size_t)b * a.OH2 + gy) * a.OW2 + gx) * 32 + grp * 8);
-    *reinterpret_cast<cn_u32x4*>(xs + p * CN_S3_PSTR + grp * 8) = v;
+      v = *reinterpret_cast<const u32x4*>(a.mid + (((size_t)b * a.OH2 + gy) * a.OW2 + gx) * 32 + grp * 8);
+    *reinterpret_cast<u32x4*>(xs + p * PSTR + grp * 8) = v;
   }
   __syncthreads();
 
   const int lr = lane & 15, lg = lane >> 4;
   const int mh = wave & 1, r0 = (wave >> 1) * 4;              // channel half (two tiles of 16) and the four pixel rows
-  const cn_u32x4* wp = reinterpret_cast<const cn_u32x4*>(a.packed3) + (size_t)(mh * 2) * (CN_TAPS * 64) + lane;
-  const unsigned short* xb = xs + ((r0 * 2) * CN_S3_IW + lr * 2) * CN_S3_PSTR + lg * 8;
-  cn_f32x4 acc[2][4];
+  const u32x4* wp = reinterpret_cast<const u32x4*>(a.packed3) + (size_t)(mh * 2) * (CN_TAPS * 64) + lane;
+  const unsigned short* xb = xs + ((r0 * 2) * CN_S3_IW + lr * 2) * PSTR + lg * 8;
+  f32x4 acc[2][4];
 #pragma unroll
   for (int m = 0; m < 2; ++m)
 #pragma unroll
-    for (int n = 0; n < 4; ++n) acc[m][n] = cn_f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int n = 0; n < 4; ++n) acc[m][n] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-#pragma unroll
-  for (int tap = 0; tap < CN_TAPS; ++tap) {
-    const int ky = tap / CN_K5, kx = tap % CN_K5;
-    cn_u32x4 af[2], bf[4];
-#pragma unroll
-    for (int m = 0; m < 2; ++m) af[m] = wp[(m * CN_TAPS + tap) * 64];
-#pragma unroll
-    for (int n = 0; n < 4; ++n) bf[n] = *reinterpret_cast<const cn_u32x4*>(xb + ((n * 2 + ky) * CN_S3_IW + kx) * CN_S3_PSTR);
-#pragma unroll
-    for (int m = 0; m < 2; ++m)
-#pragma unroll
-      for (int n = 0; n < 4; ++n) acc[m][n] = cn_mfma<BF16>(af[m], bf[n], acc[m][n]);
-  }
+  chunk_mma<BF16, 2, CN_K5, 2, CN_S3_IW>(acc, wp, (size_t)CN_TAPS * 64, 0, xb);   // one chunk: the layer-2 map has 32 channels
 
   const int ox = ox0 + lr;
 #pragma unroll
@@ -259,28 +212,28 @@ __global__ __launch_bounds__(64) void cam_head_kernel(CnHeadArgs a) {
     pix[n] = p0 + n * 16 + lr;
     in[n] = pix[n] < a.pixels;
   }
-  const cn_u32x4* wp = reinterpret_cast<const cn_u32x4*>(a.packed) + lane;
+  const u32x4* wp = reinterpret_cast<const u32x4*>(a.packed) + lane;
 
-  cn_f32x4 acc[MT][CN_HEAD_NT];
+  f32x4 acc[MT][CN_HEAD_NT];
 #pragma unroll
   for (int m = 0; m < MT; ++m)
 #pragma unroll
-    for (int n = 0; n < CN_HEAD_NT; ++n) acc[m][n] = cn_f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int n = 0; n < CN_HEAD_NT; ++n) acc[m][n] = f32x4{0.f, 0.f, 0.f, 0.f};
 
 #pragma unroll 1
   for (int ch = 0; ch < a.nch; ++ch) {
-    cn_u32x4 bf[CN_HEAD_NT];
+    u32x4 bf[CN_HEAD_NT];
 #pragma unroll
     for (int n = 0; n < CN_HEAD_NT; ++n) {
-      bf[n] = cn_u32x4{0u, 0u, 0u, 0u};
-      if (in[n]) bf[n] = *reinterpret_cast<const cn_u32x4*>(a.x + (size_t)pix[n] * a.cin + ch * 32 + lg * 8);
+      bf[n] = u32x4{0u, 0u, 0u, 0u};
+      if (in[n]) bf[n] = *reinterpret_cast<const u32x4*>(a.x + (size_t)pix[n] * a.cin + ch * 32 + lg * 8);
     }
 #pragma unroll
     for (int m = 0; m < MT; ++m) {
       if (m < a.mt) {
-        const cn_u32x4 af = wp[((size_t)m * a.nch + ch) * 64];
+        const u32x4 af = wp[((size_t)m * a.nch + ch) * 64];
 #pragma unroll
-        for (int n = 0; n < CN_HEAD_NT; ++n) acc[m][n] = cn_mfma<BF16>(af, bf[n], acc[m][n]);
+        for (int n = 0; n < CN_HEAD_NT; ++n) acc[m][n] = mfma16<BF16>(af, bf[n], acc[m][n]);
       }
     }
   }

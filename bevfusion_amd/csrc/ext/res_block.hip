@@ -6,42 +6,29 @@
 //   with downsample = Sequential(Conv2d 1x1 stride 1 or 2, BatchNorm2d): five (identity) or seven launches and every
 //   intermediate map written and read once.
 //
-// Native formulation: the implicit GEMM of bev_conv.hip (D[channel][pixel] on v_mfma_f32_16x16x32_{f16,bf16}, fp32 accumulation).
+// Native formulation: the dense conv tile of dense_tile.h.
 //   * A workgroup of four waves owns 8 x 16 output pixels x 32 * MT output channels (MT = 1, 2 or 4): wave w owns the channel half
 //     w & 1 and the four pixel rows 4 (w >> 1) ..; every pixel row of 16 is one MFMA column tile.
-//   * Phase 1 (acc2): the haloed 10 x 18 tile of h is staged in LDS in chunks of 32 channels as [pixel][32 + 8]; the nine taps read
-//     the same chunk from shifted addresses.  Phase 2 (accd, downsample mode only): only the 8 x 16 pixels (s oy, s ox) of x are
-//     staged, into the same LDS buffer, and multiplied by the 1 x 1 weight into a SECOND accumulator set.  In both phases the next
-//     chunk (the first chunk of x after the last of h) is loaded from memory into registers while the current one is multiplied.
-//     Cells outside the map and channels past the source's last are zero in LDS; no address outside a tensor is formed.
-//   * h and x carry their own layout (NCHW sources are transposed while staging).  The weights come packed in A-fragment order
-//     (bev_pack_weight; a 1 x 1 weight packs with taps = 1) and stream from L2.
-//   * Epilogue, fp32, no contraction: v = fma(acc2, scale2, shift2); r = x at the lane's own pixel and four channels (identity: one
-//     8-byte load from NHWC, four 2-byte loads from NCHW) or r = fma(accd, scale_d, shift_d); y = max(v + r, 0) rounded once.
-// Every output element is ONE accumulator chain per product in ascending (chunk, tap, ci): no atomics, no split-K; equal calls give
-// equal bits and a sample's result does not depend on the batch around it.
-#include "common.h"
-
-#pragma clang fp contract(off)
+//   * Phase 1 (acc2): the haloed 10 x 18 tile of h is staged chunk by chunk; the nine taps read the same chunk from shifted
+//     addresses.  Phase 2 (accd, downsample mode only): only the 8 x 16 pixels (s oy, s ox) of x are staged, into the same LDS
+//     buffer, and multiplied by the 1 x 1 weight into a SECOND accumulator set.  In both phases the next chunk (the first chunk of
+//     x after the last of h) is loaded from memory into registers while the current one is multiplied.
+//   * h and x carry their own layout.  The weights come from bev_pack_weight (a 1 x 1 weight packs with taps = 1).
+//   * Epilogue: v = fma(acc2, scale2, shift2); r = x at the lane's own pixel and four channels (identity) or
+//     r = fma(accd, scale_d, shift_d); y = max(v + r, 0) rounded once.
+// One accumulator chain per product; equal calls give equal bits and a sample's result does not depend on the batch around it.
+#include "dense_tile.h"
 
 namespace bevamd {
 
-typedef float rb_f32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 rb_f16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 rb_bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned int rb_u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int rb_u32x2 __attribute__((ext_vector_type(2)));
-
 constexpr int RB_TH = 8, RB_TW = 16;          // output pixels of one workgroup
-constexpr int RB_CK = 32;                     // channels of one staged chunk = one MFMA k-step per tap
-constexpr int RB_PSTR = RB_CK + 8;            // 16-bit elements per pixel in LDS (80 bytes: the padding spreads the banks)
 constexpr int RB_THREADS = 256;
 constexpr int RB_IH = RB_TH + 2, RB_IW = RB_TW + 2;          // the haloed tile of h
 constexpr int RB_NPIX = RB_IH * RB_IW;
-constexpr int RB_UNITS = RB_NPIX * (RB_CK / 8);              // a unit: 8 channels of one pixel, 16 bytes
+constexpr int RB_UNITS = RB_NPIX * (CK / 8);                 // a unit: 8 channels of one pixel, 16 bytes
 constexpr int RB_UPT = (RB_UNITS + RB_THREADS - 1) / RB_THREADS;
 constexpr int RB_XPIX = RB_TH * RB_TW;                       // the pixels of x a downsample stages
-constexpr int RB_XUNITS = RB_XPIX * (RB_CK / 8);
+constexpr int RB_XUNITS = RB_XPIX * (CK / 8);
 constexpr int RB_XUPT = RB_XUNITS / RB_THREADS;
 static_assert(RB_XUNITS % RB_THREADS == 0 && RB_XUPT <= RB_UPT, "the x tile fits the prefetch registers of the h tile");
 
@@ -63,52 +50,17 @@ struct RbArgs {
   int dst_nhwc;
 };
 
-template <bool BF16>
-__device__ __forceinline__ rb_f32x4 rb_mfma(rb_u32x4 a, rb_u32x4 b, rb_f32x4 acc) {
-  if constexpr (BF16)
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(rb_bf16x8, a), __builtin_bit_cast(rb_bf16x8, b), acc, 0, 0, 0);
-  else
-    return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(rb_f16x8, a), __builtin_bit_cast(rb_f16x8, b), acc, 0, 0, 0);
-}
-
-template <bool BF16>
-__device__ __forceinline__ unsigned short rb_round(float v) {
-  if constexpr (BF16)
-    return __builtin_bit_cast(unsigned short, (__bf16)v);
-  else
-    return __builtin_bit_cast(unsigned short, (_Float16)v);
-}
-
-template <bool BF16>
-__device__ __forceinline__ float rb_widen(unsigned short v) {
-  if constexpr (BF16)
-    return (float)__builtin_bit_cast(__bf16, v);
-  else
-    return (float)__builtin_bit_cast(_Float16, v);
-}
-
-// 8 channels [c, c + 8) of pixel (gy, gx) of sample b of a [B, cs, H, W] tensor as one 16-byte unit; the caller checked the bounds
-__device__ __forceinline__ rb_u32x4 rb_load_unit(const unsigned short* src, int nhwc, int b, int cs, int H, int W, int c, int gy, int gx) {
-  rb_u32x4 v;
-  if (nhwc) {
-    v = *reinterpret_cast<const rb_u32x4*>(src + (((size_t)b * H + gy) * W + gx) * cs + c);
-  } else {
-    const size_t hw = (size_t)H * W;
-    const unsigned short* q = src + ((size_t)b * cs + c) * hw + (size_t)gy * W + gx;
-    unsigned int e[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) e[j] = q[(size_t)j * hw];
-    v[0] = e[0] | (e[1] << 16);
-    v[1] = e[2] | (e[3] << 16);
-    v[2] = e[4] | (e[5] << 16);
-    v[3] = e[6] | (e[7] << 16);
-  }
-  return v;
+// 8 channels [c, c + 8) of pixel (gy, gx) of sample b of a [B, cs, H, W] tensor as one unit; the caller checked the bounds.  Its
+// own address arithmetic, not load_unit's base + c * cstr: that adds 35 to 48 instructions to every kernel (profiles/EXPERIMENTS.md)
+__device__ __forceinline__ u32x4 rb_load_unit(const unsigned short* src, int nhwc, int b, int cs, int H, int W, int c, int gy, int gx) {
+  if (nhwc) return *reinterpret_cast<const u32x4*>(src + (((size_t)b * H + gy) * W + gx) * cs + c);
+  const size_t hw = (size_t)H * W;
+  return gather8(src + ((size_t)b * cs + c) * hw + (size_t)gy * W + gx, hw);
 }
 
 template <bool BF16, int MT, bool DS>
 __global__ __launch_bounds__(RB_THREADS) void res_block_kernel(RbArgs a) {
-  __shared__ __attribute__((aligned(16))) unsigned short xs[RB_NPIX * RB_PSTR];
+  __shared__ __attribute__((aligned(16))) unsigned short xs[RB_NPIX * PSTR];
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int ty = blockIdx.x / a.tiles_x, tx = blockIdx.x - ty * a.tiles_x;
@@ -116,18 +68,17 @@ __global__ __launch_bounds__(RB_THREADS) void res_block_kernel(RbArgs a) {
   const int b = blockIdx.z;
   const int oy0 = ty * RB_TH, ox0 = tx * RB_TW;
 
-  rb_u32x4 pre[RB_UPT];
+  u32x4 pre[RB_UPT];
   auto load_h = [&](int ch) {
 #pragma unroll
     for (int u = 0; u < RB_UPT; ++u) {
       const int idx = tid + u * RB_THREADS;
-      rb_u32x4 v = {0u, 0u, 0u, 0u};
+      u32x4 v = {0u, 0u, 0u, 0u};
       if (idx < RB_UNITS) {
-        int p, grp;
-        if (a.h_nhwc) { grp = idx & 3; p = idx >> 2; } else { grp = idx / RB_NPIX; p = idx - grp * RB_NPIX; }
-        const int iy = p / RB_IW, ix = p - iy * RB_IW;
+        const Unit un = unit_of<RB_NPIX>(idx, a.h_nhwc);
+        const int iy = un.p / RB_IW, ix = un.p - iy * RB_IW;
         const int gy = oy0 - 1 + iy, gx = ox0 - 1 + ix;
-        const int c = ch * RB_CK + grp * 8;
+        const int c = ch * CK + un.grp * 8;
         if (gy >= 0 && gy < a.OH && gx >= 0 && gx < a.OW && c < a.C) v = rb_load_unit(a.h, a.h_nhwc, b, a.C, a.OH, a.OW, c, gy, gx);
       }
       pre[u] = v;
@@ -138,9 +89,8 @@ __global__ __launch_bounds__(RB_THREADS) void res_block_kernel(RbArgs a) {
     for (int u = 0; u < RB_UPT; ++u) {
       const int idx = tid + u * RB_THREADS;
       if (idx < RB_UNITS) {
-        int p, grp;
-        if (a.h_nhwc) { grp = idx & 3; p = idx >> 2; } else { grp = idx / RB_NPIX; p = idx - grp * RB_NPIX; }
-        *reinterpret_cast<rb_u32x4*>(xs + p * RB_PSTR + grp * 8) = pre[u];
+        const Unit un = unit_of<RB_NPIX>(idx, a.h_nhwc);
+        *reinterpret_cast<u32x4*>(xs + un.p * PSTR + un.grp * 8) = pre[u];
       }
     }
   };
@@ -149,11 +99,10 @@ __global__ __launch_bounds__(RB_THREADS) void res_block_kernel(RbArgs a) {
 #pragma unroll
     for (int u = 0; u < RB_XUPT; ++u) {
       const int idx = tid + u * RB_THREADS;
-      int p, grp;
-      if (a.x_nhwc) { grp = idx & 3; p = idx >> 2; } else { grp = idx / RB_XPIX; p = idx - grp * RB_XPIX; }
-      const int oy = oy0 + (p >> 4), ox = ox0 + (p & 15);
-      const int c = ch * RB_CK + grp * 8;
-      rb_u32x4 v = {0u, 0u, 0u, 0u};
+      const Unit un = unit_of<RB_XPIX>(idx, a.x_nhwc);
+      const int oy = oy0 + (un.p >> 4), ox = ox0 + (un.p & 15);
+      const int c = ch * CK + un.grp * 8;
+      u32x4 v = {0u, 0u, 0u, 0u};
       if (oy < a.OH && ox < a.OW && c < a.Cx) v = rb_load_unit(a.x, a.x_nhwc, b, a.Cx, a.Hx, a.Wx, c, oy * a.s, ox * a.s);
       pre[u] = v;
     }
@@ -162,9 +111,8 @@ __global__ __launch_bounds__(RB_THREADS) void res_block_kernel(RbArgs a) {
 #pragma unroll
     for (int u = 0; u < RB_XUPT; ++u) {
       const int idx = tid + u * RB_THREADS;
-      int p, grp;
-      if (a.x_nhwc) { grp = idx & 3; p = idx >> 2; } else { grp = idx / RB_XPIX; p = idx - grp * RB_XPIX; }
-      *reinterpret_cast<rb_u32x4*>(xs + p * RB_PSTR + grp * 8) = pre[u];
+      const Unit un = unit_of<RB_XPIX>(idx, a.x_nhwc);
+      *reinterpret_cast<u32x4*>(xs + un.p * PSTR + un.grp * 8) = pre[u];
     }
   };
 
@@ -172,18 +120,18 @@ __global__ __launch_bounds__(RB_THREADS) void res_block_kernel(RbArgs a) {
   const int lr = lane & 15, lg = lane >> 4;
   const int mt0 = ctile * (2 * MT) + mh * MT;            // the wave's first tile of 16 channels
 
-  rb_f32x4 acc[MT][4];
+  f32x4 acc[MT][4];
 #pragma unroll
   for (int m = 0; m < MT; ++m)
 #pragma unroll
-    for (int n = 0; n < 4; ++n) acc[m][n] = rb_f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int n = 0; n < 4; ++n) acc[m][n] = f32x4{0.f, 0.f, 0.f, 0.f};
 
   {
     // A fragment of (channel tile mt, chunk, tap): 64 lanes x 16 bytes
-    const rb_u32x4* wp = reinterpret_cast<const rb_u32x4*>(a.packed2) + ((size_t)mt0 * a.nch2) * (9 * 64) + lane;
+    const u32x4* wp = reinterpret_cast<const u32x4*>(a.packed2) + ((size_t)mt0 * a.nch2) * (9 * 64) + lane;
     const size_t wtile = (size_t)a.nch2 * (9 * 64);
     // B fragment: lane holds H[k = 8 lg + j][pixel lr] of pixel row r0 + n
-    const unsigned short* xb = xs + (r0 * RB_IW + lr) * RB_PSTR + lg * 8;
+    const unsigned short* xb = xs + (r0 * RB_IW + lr) * PSTR + lg * 8;
     load_h(0);
 #pragma unroll 1
     for (int ch = 0; ch < a.nch2; ++ch) {
@@ -191,46 +139,26 @@ __global__ __launch_bounds__(RB_THREADS) void res_block_kernel(RbArgs a) {
       __syncthreads();
       if (ch + 1 < a.nch2) load_h(ch + 1);
       else if constexpr (DS) load_x(0);
-#pragma unroll
-      for (int tap = 0; tap < 9; ++tap) {
-        const int ky = tap / 3, kx = tap % 3;
-        rb_u32x4 af[MT], bf[4];
-#pragma unroll
-        for (int m = 0; m < MT; ++m) af[m] = wp[(size_t)m * wtile + (size_t)(ch * 9 + tap) * 64];
-#pragma unroll
-        for (int n = 0; n < 4; ++n) bf[n] = *reinterpret_cast<const rb_u32x4*>(xb + ((n + ky) * RB_IW + kx) * RB_PSTR);
-#pragma unroll
-        for (int m = 0; m < MT; ++m)
-#pragma unroll
-          for (int n = 0; n < 4; ++n) acc[m][n] = rb_mfma<BF16>(af[m], bf[n], acc[m][n]);
-      }
+      chunk_mma<BF16, MT, 3, 1, RB_IW>(acc, wp, wtile, ch, xb);
       __syncthreads();   // the next chunk overwrites the tile
     }
   }
 
-  rb_f32x4 accd[DS ? MT : 1][4];
+  f32x4 accd[DS ? MT : 1][4];
   if constexpr (DS) {
 #pragma unroll
     for (int m = 0; m < MT; ++m)
 #pragma unroll
-      for (int n = 0; n < 4; ++n) accd[m][n] = rb_f32x4{0.f, 0.f, 0.f, 0.f};
-    const rb_u32x4* wp = reinterpret_cast<const rb_u32x4*>(a.packed_d) + ((size_t)mt0 * a.nchd) * 64 + lane;
+      for (int n = 0; n < 4; ++n) accd[m][n] = f32x4{0.f, 0.f, 0.f, 0.f};
+    const u32x4* wp = reinterpret_cast<const u32x4*>(a.packed_d) + ((size_t)mt0 * a.nchd) * 64 + lane;
     const size_t wtile = (size_t)a.nchd * 64;
-    const unsigned short* xb = xs + (r0 * RB_TW + lr) * RB_PSTR + lg * 8;
+    const unsigned short* xb = xs + (r0 * RB_TW + lr) * PSTR + lg * 8;
 #pragma unroll 1
     for (int ch = 0; ch < a.nchd; ++ch) {
       store_x();
       __syncthreads();
       if (ch + 1 < a.nchd) load_x(ch + 1);
-      rb_u32x4 af[MT], bf[4];
-#pragma unroll
-      for (int m = 0; m < MT; ++m) af[m] = wp[(size_t)m * wtile + (size_t)ch * 64];
-#pragma unroll
-      for (int n = 0; n < 4; ++n) bf[n] = *reinterpret_cast<const rb_u32x4*>(xb + (n * RB_TW) * RB_PSTR);
-#pragma unroll
-      for (int m = 0; m < MT; ++m)
-#pragma unroll
-        for (int n = 0; n < 4; ++n) accd[m][n] = rb_mfma<BF16>(af[m], bf[n], accd[m][n]);
+      chunk_mma<BF16, MT, 1, 1, RB_TW>(accd, wp, wtile, ch, xb);
       __syncthreads();
     }
   }
@@ -241,16 +169,9 @@ __global__ __launch_bounds__(RB_THREADS) void res_block_kernel(RbArgs a) {
 #pragma unroll
   for (int m = 0; m < MT; ++m) {
     const int co = (mt0 + m) * 16 + lg * 4;
-    const float4 sc = *reinterpret_cast<const float4*>(a.scale2 + co);
-    const float4 sh = *reinterpret_cast<const float4*>(a.shift2 + co);
-    const float s4[4] = {sc.x, sc.y, sc.z, sc.w}, t4[4] = {sh.x, sh.y, sh.z, sh.w};
-    float sd4[4] = {0.f, 0.f, 0.f, 0.f}, td4[4] = {0.f, 0.f, 0.f, 0.f};
-    if constexpr (DS) {
-      const float4 scd = *reinterpret_cast<const float4*>(a.scale_d + co);
-      const float4 shd = *reinterpret_cast<const float4*>(a.shift_d + co);
-      sd4[0] = scd.x; sd4[1] = scd.y; sd4[2] = scd.z; sd4[3] = scd.w;
-      td4[0] = shd.x; td4[1] = shd.y; td4[2] = shd.z; td4[3] = shd.w;
-    }
+    const Affine4 bn2 = load_affine4(a.scale2, a.shift2, co);
+    Affine4 bnd = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
+    if constexpr (DS) bnd = load_affine4(a.scale_d, a.shift_d, co);
 #pragma unroll
     for (int n = 0; n < 4; ++n) {
       const int oy = oy0 + r0 + n;
@@ -258,33 +179,22 @@ __global__ __launch_bounds__(RB_THREADS) void res_block_kernel(RbArgs a) {
       float res[4];
       if constexpr (DS) {
 #pragma unroll
-        for (int q = 0; q < 4; ++q) res[q] = fmaf(accd[m][n][q], sd4[q], td4[q]);
+        for (int q = 0; q < 4; ++q) res[q] = affine(accd[m][n][q], bnd, q);
       } else {
         // identity: x is [B, C, OH, OW]
         if (a.x_nhwc) {
-          const rb_u32x2 w = *reinterpret_cast<const rb_u32x2*>(a.x + (((size_t)b * a.OH + oy) * a.OW + ox) * a.C + co);
-          res[0] = rb_widen<BF16>((unsigned short)(w[0] & 0xffffu));
-          res[1] = rb_widen<BF16>((unsigned short)(w[0] >> 16));
-          res[2] = rb_widen<BF16>((unsigned short)(w[1] & 0xffffu));
-          res[3] = rb_widen<BF16>((unsigned short)(w[1] >> 16));
+          widen4<BF16>(*reinterpret_cast<const u32x2*>(a.x + (((size_t)b * a.OH + oy) * a.OW + ox) * a.C + co), res);
         } else {
           const unsigned short* q0 = a.x + ((size_t)b * a.C + co) * ohw + (size_t)oy * a.OW + ox;
 #pragma unroll
-          for (int q = 0; q < 4; ++q) res[q] = rb_widen<BF16>(q0[(size_t)q * ohw]);
+          for (int q = 0; q < 4; ++q) res[q] = widen16<BF16>(q0[(size_t)q * ohw]);
         }
       }
       unsigned short r[4];
 #pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const float v = fmaf(acc[m][n][q], s4[q], t4[q]);
-        const float y = v + res[q];
-        r[q] = rb_round<BF16>(y > 0.f ? y : 0.f);
-      }
+      for (int q = 0; q < 4; ++q) r[q] = round16<BF16>(relu(affine(acc[m][n][q], bn2, q) + res[q]));
       if (a.dst_nhwc) {
-        rb_u32x2 o;
-        o[0] = (unsigned int)r[0] | ((unsigned int)r[1] << 16);
-        o[1] = (unsigned int)r[2] | ((unsigned int)r[3] << 16);
-        *reinterpret_cast<rb_u32x2*>(a.dst + (((size_t)b * a.OH + oy) * a.OW + ox) * a.C + co) = o;
+        *reinterpret_cast<u32x2*>(a.dst + (((size_t)b * a.OH + oy) * a.OW + ox) * a.C + co) = pack4(r[0], r[1], r[2], r[3]);
       } else {
         unsigned short* d = a.dst + ((size_t)b * a.C + co) * ohw + (size_t)oy * a.OW + ox;
 #pragma unroll
@@ -303,11 +213,6 @@ static void rb_launch(const RbArgs& a, int batch, hipStream_t stream) {
     res_block_kernel<BF16, 2, DS><<<dim3(tiles, a.C / 64, batch), dim3(RB_THREADS), 0, stream>>>(a);
   else
     res_block_kernel<BF16, 1, DS><<<dim3(tiles, a.C / 32, batch), dim3(RB_THREADS), 0, stream>>>(a);
-}
-
-static bool rb_overlap(const void* p, long long pbytes, const void* q, long long qbytes) {
-  const uintptr_t a = (uintptr_t)p, b = (uintptr_t)q;
-  return a < b + (uintptr_t)qbytes && b < a + (uintptr_t)pbytes;
 }
 
 }  // namespace bevamd
@@ -354,10 +259,10 @@ int bevamd_res_block_forward(const void* h, int h_layout, const void* x, int x_l
                    "res_block_forward: the identity residual needs x [%d, %d, %d] equal to the output [%d, %d, %d] at stride 1, got stride %d",
                    x_channels, x_height, x_width, channels, out_height, out_width, stride);
   }
-  const int nch2 = channels / RB_CK, nchd = ds ? (x_channels + RB_CK - 1) / RB_CK : 0;
-  const long long want2 = (long long)channels * nch2 * 9 * RB_CK;
+  const int nch2 = channels / CK, nchd = ds ? (x_channels + CK - 1) / CK : 0;
+  const long long want2 = (long long)channels * nch2 * 9 * CK;
   BEVAMD_REQUIRE(packed2_elems == want2, "res_block_forward: packed2 holds %lld elements, this block needs %lld", packed2_elems, want2);
-  const long long wantd = (long long)channels * nchd * RB_CK;
+  const long long wantd = (long long)channels * nchd * CK;
   BEVAMD_REQUIRE(packed_d_elems == wantd, "res_block_forward: packed_d holds %lld elements, this block needs %lld", packed_d_elems, wantd);
   const long long want_dst = (long long)batch * channels * out_height * (long long)out_width;
   BEVAMD_REQUIRE(dst_elems == want_dst, "res_block_forward: dst holds %lld elements, [%d, %d, %d, %d] needs %lld", dst_elems, batch,
@@ -379,7 +284,7 @@ int bevamd_res_block_forward(const void* h, int h_layout, const void* x, int x_l
   BEVAMD_REQUIRE((((uintptr_t)h | (uintptr_t)x | (uintptr_t)dst) & 1) == 0, "res_block_forward: h, x or dst is not 2-byte aligned");
   BEVAMD_REQUIRE(dst_layout == 0 || ((uintptr_t)dst & 7) == 0, "res_block_forward: an NHWC dst is not 8-byte aligned");
   const long long x_bytes = 2LL * batch * x_channels * x_height * (long long)x_width;
-  BEVAMD_REQUIRE(!rb_overlap(dst, 2 * want_dst, h, 2 * want_dst) && !rb_overlap(dst, 2 * want_dst, x, x_bytes),
+  BEVAMD_REQUIRE(!ranges_overlap(dst, 2 * want_dst, h, 2 * want_dst) && !ranges_overlap(dst, 2 * want_dst, x, x_bytes),
                  "res_block_forward: dst overlaps h or x");
 
   RbArgs a;

@@ -5,8 +5,8 @@
 //     x = self.conv1(x);  x = self.norm1(x);  x = self.relu(x);  x = self.maxpool(x)
 //   four launches, the 64-channel half-resolution map written and read three times to produce a map a quarter its size.
 //
-// Native formulation: implicit GEMM D[channel][conv pixel] on v_mfma_f32_16x16x32_{f16,bf16} with fp32 accumulation; the conv map
-// never reaches memory.
+// Native formulation: implicit GEMM D[channel][conv pixel] with the MFMA, the fragment layouts and the epilogue pieces of
+// dense_tile.h, its own staging and B operand; the conv map never reaches memory.
 //   * A workgroup of four waves owns 4 x 15 pooled pixels x 64 channels of one image.  They need the 9 x 31 conv pixels from
 //     (2 ph0 - 1, 2 pw0 - 1); the workgroup computes 9 x 32 (18 MFMA column tiles of 16 conv pixels of one conv row, dealt to the
 //     waves round robin) from the 23 x 70 x 3 input tile from (4 ph0 - 5, 4 pw0 - 5), staged once in LDS as [ci][row][72] with
@@ -20,17 +20,9 @@
 //     Rounding is monotone, so the maximum of the rounded values IS the rounded maximum of the fp32 values.
 // Every conv value is ONE accumulator chain in ascending k: no atomics, no split-K; equal calls give equal bits and a sample's
 // result does not depend on the batch around it.
-#include "common.h"
-
-#pragma clang fp contract(off)
+#include "dense_tile.h"
 
 namespace bevamd {
-
-typedef float st_f32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 st_f16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 st_bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned int st_u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int st_u32x2 __attribute__((ext_vector_type(2)));
 
 constexpr int ST_TPH = 4, ST_TPW = 15;                        // pooled pixels of one workgroup
 constexpr int ST_CH = 2 * ST_TPH + 1, ST_CW = 32;             // conv pixels it computes (31 columns are pooled)
@@ -55,30 +47,6 @@ struct StArgs {
   unsigned short* dst;
   int dst_nhwc;
 };
-
-template <bool BF16>
-__device__ __forceinline__ st_f32x4 st_mfma(st_u32x4 a, st_u32x4 b, st_f32x4 acc) {
-  if constexpr (BF16)
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(st_bf16x8, a), __builtin_bit_cast(st_bf16x8, b), acc, 0, 0, 0);
-  else
-    return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(st_f16x8, a), __builtin_bit_cast(st_f16x8, b), acc, 0, 0, 0);
-}
-
-template <bool BF16>
-__device__ __forceinline__ unsigned short st_round(float v) {
-  if constexpr (BF16)
-    return __builtin_bit_cast(unsigned short, (__bf16)v);
-  else
-    return __builtin_bit_cast(unsigned short, (_Float16)v);
-}
-
-template <bool BF16>
-__device__ __forceinline__ float st_widen(unsigned short v) {
-  if constexpr (BF16)
-    return (float)__builtin_bit_cast(__bf16, v);
-  else
-    return (float)__builtin_bit_cast(_Float16, v);
-}
 
 template <bool BF16>
 __global__ __launch_bounds__(ST_THREADS) void resnet_stem_kernel(StArgs a) {
@@ -109,9 +77,9 @@ __global__ __launch_bounds__(ST_THREADS) void resnet_stem_kernel(StArgs a) {
 
   const int lr = lane & 15, lg = lane >> 4;
   // A fragments: [mt][kstep][lane] units of 16 bytes, all 24 in registers
-  st_u32x4 af[4][ST_KSTEPS];
+  u32x4 af[4][ST_KSTEPS];
   {
-    const st_u32x4* wp = reinterpret_cast<const st_u32x4*>(a.packed) + lane;
+    const u32x4* wp = reinterpret_cast<const u32x4*>(a.packed) + lane;
 #pragma unroll
     for (int m = 0; m < 4; ++m)
 #pragma unroll
@@ -128,34 +96,29 @@ __global__ __launch_bounds__(ST_THREADS) void resnet_stem_kernel(StArgs a) {
     const int ci = pc / 7, ky = pc - 7 * ci;
     rowoff[ks] = (ci * ST_IH + ky) * ST_RS;
   }
-  float s4[4][4], t4[4][4];
+  Affine4 bn[4];
 #pragma unroll
-  for (int m = 0; m < 4; ++m) {
-    const float4 sc = *reinterpret_cast<const float4*>(a.scale + 16 * m + 4 * lg);
-    const float4 sh = *reinterpret_cast<const float4*>(a.shift + 16 * m + 4 * lg);
-    s4[m][0] = sc.x; s4[m][1] = sc.y; s4[m][2] = sc.z; s4[m][3] = sc.w;
-    t4[m][0] = sh.x; t4[m][1] = sh.y; t4[m][2] = sh.z; t4[m][3] = sh.w;
-  }
+  for (int m = 0; m < 4; ++m) bn[m] = load_affine4(a.scale, a.shift, 16 * m + 4 * lg);
   __syncthreads();
 
 #pragma unroll 1
   for (int t = wave; t < ST_TILES; t += 4) {
     const int r = t >> 1, c = (t & 1) * 16 + lr;             // the lane's conv pixel of the tile
     const unsigned short* src = in_s + (2 * r) * ST_RS + 2 * c;
-    st_f32x4 acc[4];
+    f32x4 acc[4];
 #pragma unroll
-    for (int m = 0; m < 4; ++m) acc[m] = st_f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int m = 0; m < 4; ++m) acc[m] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int ks = 0; ks < ST_KSTEPS; ++ks) {
       const unsigned int* q = reinterpret_cast<const unsigned int*>(src + rowoff[ks]);
-      st_u32x4 bf;
+      u32x4 bf;
       bf[0] = q[0];
       bf[1] = q[1];
       bf[2] = q[2];
       bf[3] = q[3] & 0xffffu;                                // the eighth pixel is outside the 7 x 7 window
-      if (!pair_live[ks]) bf = st_u32x4{0u, 0u, 0u, 0u};
+      if (!pair_live[ks]) bf = u32x4{0u, 0u, 0u, 0u};
 #pragma unroll
-      for (int m = 0; m < 4; ++m) acc[m] = st_mfma<BF16>(af[m][ks], bf, acc[m]);
+      for (int m = 0; m < 4; ++m) acc[m] = mfma16<BF16>(af[m][ks], bf, acc[m]);
     }
     // D fragment: pixel on the lane (lr), channel = 16 m + 4 lg + reg
     unsigned short* d = conv_s + (r * ST_CW + c) * ST_CSTR + 4 * lg;
@@ -163,14 +126,8 @@ __global__ __launch_bounds__(ST_THREADS) void resnet_stem_kernel(StArgs a) {
     for (int m = 0; m < 4; ++m) {
       unsigned short v[4];
 #pragma unroll
-      for (int q4 = 0; q4 < 4; ++q4) {
-        const float y = fmaf(acc[m][q4], s4[m][q4], t4[m][q4]);
-        v[q4] = st_round<BF16>(y > 0.f ? y : 0.f);
-      }
-      st_u32x2 o;
-      o[0] = (unsigned int)v[0] | ((unsigned int)v[1] << 16);
-      o[1] = (unsigned int)v[2] | ((unsigned int)v[3] << 16);
-      *reinterpret_cast<st_u32x2*>(d + 16 * m) = o;
+      for (int q4 = 0; q4 < 4; ++q4) v[q4] = round16<BF16>(relu(affine(acc[m][q4], bn[m], q4)));
+      *reinterpret_cast<u32x2*>(d + 16 * m) = pack4(v[0], v[1], v[2], v[3]);
     }
   }
   __syncthreads();
@@ -194,10 +151,10 @@ __global__ __launch_bounds__(ST_THREADS) void resnet_stem_kernel(StArgs a) {
         const int r = 2 * i + dy, c = 2 * j + dx;
         const int cy = cy0 + r, cx = cx0 + c;
         if (cy < 0 || cy >= a.OH || cx < 0 || cx >= a.OW) continue;     // cells outside the conv map do not take part
-        const st_u32x4 w = *reinterpret_cast<const st_u32x4*>(conv_s + (r * ST_CW + c) * ST_CSTR + 8 * g);
+        const u32x4 w = *reinterpret_cast<const u32x4*>(conv_s + (r * ST_CW + c) * ST_CSTR + 8 * g);
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-          const float lo = st_widen<BF16>((unsigned short)(w[e] & 0xffffu)), hi = st_widen<BF16>((unsigned short)(w[e] >> 16));
+          const float lo = widen16<BF16>((unsigned short)(w[e] & 0xffffu)), hi = widen16<BF16>((unsigned short)(w[e] >> 16));
           best[2 * e] = any ? fmaxf(best[2 * e], lo) : lo;
           best[2 * e + 1] = any ? fmaxf(best[2 * e + 1], hi) : hi;
         }
@@ -206,23 +163,18 @@ __global__ __launch_bounds__(ST_THREADS) void resnet_stem_kernel(StArgs a) {
     }
     unsigned short v[8];
 #pragma unroll
-    for (int e = 0; e < 8; ++e) v[e] = st_round<BF16>(best[e]);          // exact: the values are 16-bit already
+    for (int e = 0; e < 8; ++e) v[e] = round16<BF16>(best[e]);          // exact: the values are 16-bit already
     if (a.dst_nhwc) {
-      st_u32x4 o;
+      u32x4 o;
 #pragma unroll
       for (int e = 0; e < 4; ++e) o[e] = (unsigned int)v[2 * e] | ((unsigned int)v[2 * e + 1] << 16);
-      *reinterpret_cast<st_u32x4*>(a.dst + (((size_t)b * a.PH + ph) * a.PW + pw) * 64 + 8 * g) = o;
+      *reinterpret_cast<u32x4*>(a.dst + (((size_t)b * a.PH + ph) * a.PW + pw) * 64 + 8 * g) = o;
     } else {
       unsigned short* d = a.dst + ((size_t)b * 64 + 8 * g) * phw + (size_t)ph * a.PW + pw;
 #pragma unroll
       for (int e = 0; e < 8; ++e) d[(size_t)e * phw] = v[e];
     }
   }
-}
-
-static bool st_overlap(const void* p, long long pbytes, const void* q, long long qbytes) {
-  const uintptr_t a = (uintptr_t)p, b = (uintptr_t)q;
-  return a < b + (uintptr_t)qbytes && b < a + (uintptr_t)pbytes;
 }
 
 }  // namespace bevamd
@@ -267,7 +219,7 @@ int bevamd_resnet_stem_forward(const void* x, int dtype, int batch, int in_chann
   BEVAMD_REQUIRE((((uintptr_t)x | (uintptr_t)dst) & 1) == 0, "resnet_stem_forward: x or dst is not 2-byte aligned");
   BEVAMD_REQUIRE(dst_layout == 0 || ((uintptr_t)dst & 15) == 0, "resnet_stem_forward: an NHWC dst is not 16-byte aligned");
   const long long x_bytes = 2LL * batch * 3 * height * (long long)width;
-  BEVAMD_REQUIRE(!st_overlap(dst, 2 * want_dst, x, x_bytes), "resnet_stem_forward: dst overlaps x");
+  BEVAMD_REQUIRE(!ranges_overlap(dst, 2 * want_dst, x, x_bytes), "resnet_stem_forward: dst overlaps x");
 
   StArgs a;
   a.x = (const unsigned short*)x;
