@@ -179,6 +179,8 @@ _EXT_SIGNATURES = {
     # camera ResNet: the Bottleneck tail (conv3 + BatchNorm + residual + ReLU) and the stem (conv 7x7 + BatchNorm + ReLU + MaxPool)
     "bevamd_bottleneck_tail_forward": (I, [P, I, I, P, I, I, I, I, I, I, I, I, I, I, I, P, LL, P, P, P, LL, P, P, P, I, LL, P]),
     "bevamd_resnet_stem_forward": (I, [P, I, I, I, I, I, I, I, I, I, I, I, I, I, P, LL, P, P, P, I, LL, P]),
+    # camera Swin: shifted-window attention between the qkv and the proj Linear
+    "bevamd_window_attention_forward": (I, [P, LL, P, LL, P, LL, I, I, I, I, I, I, I, I, c_float, I, P, LL, P]),
     # camera necks: resampling + cat + convolution + BatchNorm + ReLU
     "bevamd_neck_conv_forward": (I, [P, I, I, I, I, P, I, I, I, I, I, I, I, I, I, I, P, LL, P, P, I, P, I, I, I, LL, P]),
     # camera depth nets: the depth stem and the depthnet's softmax head

@@ -33,7 +33,10 @@ mmdet3d/core/bbox/coders/transfusion_bbox_coder.py, mmdet3d/core/post_processing
   * `ResNet`, `Bottleneck`, `bottleneck_tail_forward`, `fold_bottleneck`, `bottleneck_spec`, `stem_forward`, `fold_stem`,
     `stem_spec`, `stem_pack_weight`, `stem_unpack_weight`: the camera backbone of the ResNet-50 configs as a module and its fused
     Bottleneck tail (conv3 + BatchNorm + residual + ReLU) and stem (conv 7x7 + BatchNorm + ReLU + MaxPool) for eval mode,
-    re-exported from `cam_resnet`.
+    re-exported from `cam_resnet`;
+  * `SwinTransformer`, `SwinBlockSequence`, `SwinBlock`, `ShiftWindowMSA`, `WindowMSA`, `PatchEmbed`, `PatchMerging`, `SwinFFN`
+    (mmcv's FFN, `cam_swin.FFN`; `heads.FFN` stays the TransFusion head's), `DropPath`, `window_attention`, `fold_window_bias`, `window_attention_spec`, `swin_convert`: the camera backbone of the Swin-T
+    configs as a module and its fused shifted-window attention for eval mode, re-exported from `cam_swin`.
 
 Dispatch: device tensors go through the library or raise (no torch formulation for them); host tensors run the reference's
 formulation written in torch / numpy with a STABLE descending argsort, which is the order the kernels are defined to produce
@@ -55,6 +58,9 @@ from .bev_resnet import (BasicBlock, FoldedResBlock, GeneralizedResNet, fold_res
                          res_block_forward, res_block_spec)                 # (the residual BEV backbone)
 from .cam_resnet import (Bottleneck, FoldedBottleneckTail, FoldedStem, ResNet, bottleneck_spec, bottleneck_tail_forward,  # noqa: F401
                          fold_bottleneck, fold_stem, stem_forward, stem_pack_weight, stem_spec, stem_unpack_weight)  # (the camera ResNet)
+from .cam_swin import (DropPath, PatchEmbed, PatchMerging, ShiftWindowMSA, SwinBlock, SwinBlockSequence, SwinFFN,  # noqa: F401
+                       SwinTransformer, WindowMSA, fold_window_bias, swin_convert, window_attention,
+                       window_attention_spec)                               # (the camera Swin Transformer)
 from .cam_nets import (DepthHeadFold, DepthStemFold, depth_head_forward, depth_stem_forward, fold_conv_bias_bn,  # noqa: F401
                        fold_depth_head, fold_depth_stem)                    # (the camera depth nets)
 from .cam_neck import (LSSFPN, GeneralizedLSSFPN, cam_neck_conv_forward, fold_conv_bias, fold_neck_layer,  # noqa: F401
@@ -86,7 +92,9 @@ __all__ = ["circle_nms", "circle_nms_segments", "TransFusionBBoxCoder", "Proposa
            "LSSFPN", "cam_neck_conv_forward", "fold_conv_bias", "fold_neck_layer", "neck_layer_spec", "GeneralizedResNet", "BasicBlock",
            "make_res_layer", "FoldedResBlock", "fold_res_block", "res_block_forward", "res_block_spec",
            "ResNet", "Bottleneck", "FoldedBottleneckTail", "FoldedStem", "bottleneck_spec", "fold_bottleneck", "bottleneck_tail_forward",
-           "stem_spec", "fold_stem", "stem_forward", "stem_pack_weight", "stem_unpack_weight"]
+           "stem_spec", "fold_stem", "stem_forward", "stem_pack_weight", "stem_unpack_weight",
+           "SwinTransformer", "SwinBlockSequence", "SwinBlock", "ShiftWindowMSA", "WindowMSA", "PatchEmbed", "PatchMerging", "SwinFFN",
+           "DropPath", "window_attention", "fold_window_bias", "window_attention_spec", "swin_convert"]
 
 MAX_PROPOSALS = 1024     # HE_MAX_K of the kernels: proposals per sample, rows per NMS segment
 _UNSUPPORTED = 4

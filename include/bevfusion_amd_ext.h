@@ -351,6 +351,32 @@ int bevamd_resnet_stem_forward(const void* x, int dtype, int batch, int in_chann
                                const float* shift, void* dst, int dst_layout, long long dst_elems, void* stream);
 
 
+/* The shifted-window attention of a Swin block in eval mode (mmdet 2.x mmdet/models/backbones/swin.py ShiftWindowMSA + WindowMSA
+ * between the qkv and the proj Linear): pad, roll, window partition, q k^T, relative position bias, shift mask, softmax, attn v,
+ * window reverse, roll back and crop in ONE launch on 16-bit storage (dtype 0: fp16, 1: bf16) with fp32 accumulation on
+ * v_mfma_f32_16x16x32; no workspace, no device synchronisation, no atomics: equal calls give bit-equal results, a sample's result
+ * does not depend on the batch, and the call can be captured in a graph.
+ *
+ * bevamd_window_attention_forward: qkv [batch, height, width, 3 * channels] contiguous, 16-byte aligned (qkv_elems elements), the
+ *   qkv Linear of the un-padded, un-rolled token map with channel which * channels + head * 32 + d (which 0: q, 1: k, 2: v).
+ *   pad_qkv [3 * channels] (pad_elems = 3 * channels), 16-byte aligned: the q, k, v of a padded token (the Linear's bias), or null
+ *   with pad_elems 0 for zeros.  bias [heads, 49, 49] fp32 (bias_elems floats): the dense relative position bias [head][query][key].
+ *   With Hp, Wp = height, width rounded up to 7, token (ty, tx) of window (wy, wx) is pixel y = (7 wy + ty + shift) mod Hp,
+ *   x = (7 wx + tx + shift) mod Wp when y < height and x < width, else the padded token (which takes part as a key, and whose
+ *   output is not written).  region(r) = 0 if r < Hp - 7, 1 if r < Hp - shift, else 2 of the rolled row r = 7 wy + ty, columns alike;
+ *     logit[i][j] = fma(sum_d q_i[d] k_j[d], scale, bias[head][i][j]) + (shift > 0 and regions of i and j differ ? -100 : 0)
+ *     p = exp(logit - max_j logit),  out_i[d] = round16((sum_j round16(p[i][j]) v_j[d]) / sum_j p[i][j])
+ *   in fp32.  out [batch, height, width, channels] (out_elems elements), 8-byte aligned: every element is written, nothing else,
+ *   and qkv is only read inside its extent.  out must not overlap qkv, pad_qkv or bias.
+ *   Limits, checked on the host before any GPU work, anything else returns 4 (unsupported): window 7, head_dim 32.  channels =
+ *   heads * 32, 0 <= shift < 7, map >= 1 x 1, batch >= 0 (0: nothing to do, qkv and out may be null).  Code 1: a null or misaligned
+ *   pointer, a bad dtype, bad sizes, qkv_elems, pad_elems, bias_elems or out_elems that do not fit, an overlap.  The entry cannot
+ *   tell a host pointer from a device pointer (the Python wrapper refuses host tensors). */
+int bevamd_window_attention_forward(const void* qkv, long long qkv_elems, const void* pad_qkv, long long pad_elems, const float* bias,
+                                    long long bias_elems, int dtype, int batch, int height, int width, int channels, int heads,
+                                    int window, int head_dim, float scale, int shift, void* out, long long out_elems, void* stream);
+
+
 /* One layer of the camera necks in eval mode (mmdet3d/models/necks/generalized_lss.py GeneralizedLSSFPN, models/necks/lss.py
  * LSSFPN): F.interpolate(bilinear, align_corners=True) + torch.cat + convolution + folded BatchNorm + optional ReLU in ONE launch
  * on 16-bit storage (dtype 0: fp16, 1: bf16) with fp32 accumulation on v_mfma_f32_16x16x32; no workspace, no device
