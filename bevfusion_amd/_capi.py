@@ -181,6 +181,8 @@ _EXT_SIGNATURES = {
     "bevamd_resnet_stem_forward": (I, [P, I, I, I, I, I, I, I, I, I, I, I, I, I, P, LL, P, P, P, I, LL, P]),
     # camera Swin: shifted-window attention between the qkv and the proj Linear
     "bevamd_window_attention_forward": (I, [P, LL, P, LL, P, LL, I, I, I, I, I, I, I, I, c_float, I, P, LL, P]),
+    # camera Swin: LayerNorm + fc1 + GELU + fc2 + residual of a block
+    "bevamd_swin_ffn_forward": (I, [P, LL, P, LL, P, LL, P, LL, P, LL, P, LL, P, LL, I, LL, I, I, c_float, P, LL, P]),
     # camera necks: resampling + cat + convolution + BatchNorm + ReLU
     "bevamd_neck_conv_forward": (I, [P, I, I, I, I, P, I, I, I, I, I, I, I, I, I, I, P, LL, P, P, I, P, I, I, I, LL, P]),
     # camera depth nets: the depth stem and the depthnet's softmax head

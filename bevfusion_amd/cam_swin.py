@@ -19,6 +19,9 @@ Dispatch, as `cam_resnet.ResNet` does it:
     the `proj` Linear (torch) -> residual.  The Linear layers, the LayerNorms and the FFN stay with torch.  A block whose window or
     head size the kernel does not serve (anything but 7 and 32), or whose stage is not in `fused_stages`, runs its torch layers
     inside the chain.
+  * on that path, a block of a stage listed in `fused_ffn_stages` (default: none) ends in ONE launch of `bevamd_swin_ffn_forward`
+    (csrc/ext/swin_ffn.hip: `norm2`, fc1, GELU, fc2 and the residual, the hidden activations in registers) where `swin_ffn_spec`
+    holds; any other block ends in its torch layers.
   * otherwise (train mode, host tensors, fp32 tensors, a gradient, `use_fused = False`): the torch layers in mmdet's order, with
     autograd, dropout and drop-path.
 
@@ -26,7 +29,7 @@ Fused outputs are logical [B, C, H, W] tensors with channels-last strides (the t
 `GeneralizedLSSFPN` reads in place.  No host sync; the dense relative position bias of a block is expanded once and cached on its
 `WindowMSA` (`fold_window_bias`), so the eval forward can be captured in a `torch.cuda.graph` after one warm-up forward.
 
-`use_fused` and `fused_stages` follow the measurement in DESIGN 3.29.
+`use_fused` and `fused_stages` follow the measurement in DESIGN 3.29, `fused_ffn_stages` the one in DESIGN 3.30.
 """
 import math
 from collections import OrderedDict
@@ -40,11 +43,13 @@ from .bev_trunk import _DTYPES, _fusable_tensor, _no_grad_needed, _tensor_key
 from .registry import BACKBONES, build_norm_layer, register_everywhere  # noqa: F401
 
 __all__ = ["SwinTransformer", "SwinBlockSequence", "SwinBlock", "ShiftWindowMSA", "WindowMSA", "PatchEmbed", "PatchMerging", "SwinFFN",
-           "DropPath", "window_attention", "fold_window_bias", "window_attention_spec", "swin_convert"]
+           "DropPath", "window_attention", "fold_window_bias", "window_attention_spec", "swin_convert", "swin_ffn", "fold_swin_ffn",
+           "swin_ffn_spec", "swin_pack_ffn"]
 
 _UNSUPPORTED = 4          # BEVAMD_ERR_UNSUPPORTED
 KERNEL_WINDOW = 7
 KERNEL_HEAD_DIM = 32
+KERNEL_FFN_CMAX = 192     # SF_CMAX of csrc/ext/swin_ffn.hip: the widest token of the fused FFN; its hidden width goes to 4 times that
 _DEFAULT_NORM = dict(type="LN")
 _DEFAULT_ACT = dict(type="GELU")
 
@@ -369,7 +374,9 @@ class ShiftWindowMSA(nn.Module):
 
 
 class SwinBlock(nn.Module):
-    """norm1 - ShiftWindowMSA - residual, norm2 - FFN (the residual inside).  forward(x [B, L, C], (H, W))."""
+    """norm1 - ShiftWindowMSA - residual, norm2 - FFN (the residual inside).  forward(x [B, L, C], (H, W)); `fused`: the attention
+    through its kernel, `fused_ffn`: norm2 - FFN through `swin_ffn`, each where the block is served (eval mode on the device: the
+    caller decides)."""
 
     def __init__(self, embed_dims, num_heads, feedforward_channels, window_size=7, shift=False, qkv_bias=True, qk_scale=None,
                  drop_rate=0.0, attn_drop_rate=0.0, drop_path_rate=0.0, act_cfg=None, norm_cfg=None, with_cp=False):
@@ -384,13 +391,17 @@ class SwinBlock(nn.Module):
         self.norm2 = build_norm_layer(norm_cfg, embed_dims)[1]
         self.ffn = FFN(embed_dims, feedforward_channels, 2, act_cfg, drop_rate, dict(type="DropPath", drop_prob=drop_path_rate), True)
 
-    def forward(self, x, hw_shape, fused=False):
+    def forward(self, x, hw_shape, fused=False, fused_ffn=False):
         identity = x
         h = self.norm1(x)
         a = self.attn.forward_fused(h, hw_shape) if fused and window_attention_spec(self.attn) else None
         if a is None:
             a = self.attn(h, hw_shape)
         x = a + identity
+        if fused_ffn and swin_ffn_spec(self):
+            y = _swin_ffn_served(x, self.norm2, self.ffn)
+            if y is not None:
+                return y
         return self.ffn(self.norm2(x), identity=x)
 
 
@@ -408,9 +419,9 @@ class SwinBlockSequence(nn.Module):
                       rates[i], act_cfg, norm_cfg, with_cp) for i in range(depth))
         self.downsample = downsample
 
-    def forward(self, x, hw_shape, fused=False):
+    def forward(self, x, hw_shape, fused=False, fused_ffn=False):
         for block in self.blocks:
-            x = block(x, hw_shape, fused)
+            x = block(x, hw_shape, fused, fused_ffn)
         if self.downsample is not None:
             x_down, down_hw = self.downsample(x, hw_shape)
             return x_down, down_hw, x, hw_shape
@@ -429,6 +440,9 @@ class SwinTransformer(nn.Module):
     # defaults from the measurement in DESIGN 3.29
     use_fused = True                 # eval mode on GPU fp16 / bf16 tensors: the attention of every served block through the kernel
     fused_stages = (0, 1, 2, 3)      # the stages whose blocks do
+    # opt-in, measurement in DESIGN 3.30: the stages whose served blocks end in one launch of the fused FFN (consulted only where
+    # `fusable` holds)
+    fused_ffn_stages = ()
 
     def __init__(self, pretrain_img_size=224, in_channels=3, embed_dims=96, patch_size=4, window_size=7, mlp_ratio=4,
                  depths=(2, 2, 6, 2), num_heads=(3, 6, 12, 24), strides=(4, 2, 2, 2), out_indices=(0, 1, 2, 3), qkv_bias=True,
@@ -525,12 +539,115 @@ class SwinTransformer(nn.Module):
         x = self.drop_after_pos(x)
         outs = []
         for i, stage in enumerate(self.stages):
-            x, hw_shape, out, out_hw = stage(x, hw_shape, fused and i in self.fused_stages)
+            x, hw_shape, out, out_hw = stage(x, hw_shape, fused and i in self.fused_stages, fused and i in self.fused_ffn_stages)
             if i in self.out_indices:
                 out = getattr(self, f"norm{i}")(out)
                 out = out.view(-1, *out_hw, self.num_features[i]).permute(0, 3, 1, 2)
                 outs.append(out if fused else out.contiguous())
         return tuple(outs)
+
+
+def swin_pack_ffn(w1, w2):
+    """fc1.weight [hidden, C] and fc2.weight [C, hidden] in the MFMA fragment order of csrc/ext/swin_ffn.hip (both multiples of 32):
+    packed1[tile][ks][lane][e] = w1[16 tile + (lane & 15)][32 ks + 8 (lane >> 4) + e], packed2[s][ct][lane][e] = w2[16 ct + (lane & 15)]
+    [32 s + 16 (e >> 2) + 4 (lane >> 4) + (e & 3)].  Returns two flat contiguous tensors of the inputs' dtype and device."""
+    hidden, C = w1.shape
+    if tuple(w2.shape) != (C, hidden) or C % 32 or hidden % 32:
+        raise ValueError(f"fc1 {tuple(w1.shape)} and fc2 {tuple(w2.shape)} must be [hidden, C] and [C, hidden], both multiples of 32")
+    # w1: [tile, lane & 15, ks, lane >> 4, e] -> [tile, ks, lane >> 4, lane & 15, e]
+    p1 = w1.detach().reshape(hidden // 16, 16, C // 32, 4, 8).permute(0, 2, 3, 1, 4).contiguous().view(-1)
+    # w2: [ct, lane & 15, s, e >> 2, lane >> 4, e & 3] -> [s, ct, lane >> 4, lane & 15, e >> 2, e & 3]
+    p2 = w2.detach().reshape(C // 16, 16, hidden // 32, 2, 4, 4).permute(2, 0, 4, 1, 3, 5).contiguous().view(-1)
+    return p1, p2
+
+
+def _ffn_linears(ffn):
+    return ffn.layers[0][0], ffn.layers[1]
+
+
+def fold_swin_ffn(norm, ffn):
+    """(packed1, packed2, gamma, beta, b1, b2) of a block's `norm2` and `ffn` for `bevamd_swin_ffn_forward`: the two weights in
+    fragment order (`swin_pack_ffn`) and the LayerNorm's and the Linears' vectors widened to fp32 (exact), cached on `ffn` on the
+    tensors' addresses and versions (see `fold_bev_layer` for what moves a version); None for widths that are no multiples of 32,
+    which have no fragment order.  Run one forward before capturing a graph."""
+    fc1, fc2 = _ffn_linears(ffn)
+    tensors = [norm.weight, norm.bias, fc1.weight, fc1.bias, fc2.weight, fc2.bias]
+    key = _tensor_key(tensors)
+    cache = ffn.__dict__.get("_bevamd_folded")
+    if cache is not None and cache[0] == key:
+        return cache[1]
+    val = None
+    if fc1.weight.shape[0] % 32 == 0 and fc1.weight.shape[1] % 32 == 0:
+        val = swin_pack_ffn(fc1.weight, fc2.weight) + tuple(t.detach().to(torch.float32).contiguous() for t in
+                                                            (norm.weight, norm.bias, fc1.bias, fc2.bias))
+    ffn.__dict__["_bevamd_folded"] = (key, val)
+    return val
+
+
+def _ffn_modules_served(norm, ffn):
+    """The structure `bevamd_swin_ffn_forward` computes: an affine LayerNorm over the last dimension, Linear - exact GELU - Linear
+    with biases, the identity added."""
+    if not isinstance(norm, nn.LayerNorm) or not isinstance(ffn, FFN) or ffn.num_fcs != 2 or not ffn.add_identity:
+        return False
+    fc1, fc2 = _ffn_linears(ffn)
+    act = ffn.layers[0][1]
+    C = ffn.embed_dims
+    return norm.weight is not None and norm.bias is not None and tuple(norm.normalized_shape) == (C,) \
+        and type(act) is nn.GELU and getattr(act, "approximate", "none") == "none" \
+        and fc1.bias is not None and fc2.bias is not None and fc1.in_features == C and fc2.out_features == C \
+        and fc1.out_features == fc2.in_features
+
+
+def swin_ffn_spec(block):
+    """True for a `SwinBlock` whose tail the kernel serves: `norm2` an affine nn.LayerNorm over C, an FFN of two Linears around an
+    exact nn.GELU with the identity added, C a multiple of 32 up to 192 and the hidden width a multiple of 32 up to 768."""
+    norm, ffn = getattr(block, "norm2", None), getattr(block, "ffn", None)
+    if not _ffn_modules_served(norm, ffn):
+        return False
+    C, hidden = ffn.embed_dims, ffn.layers[0][0].out_features
+    return C % 32 == 0 and 32 <= C <= KERNEL_FFN_CMAX and hidden % 32 == 0 and 32 <= hidden <= 4 * KERNEL_FFN_CMAX
+
+
+def swin_ffn(x, norm, ffn, *, out=None):
+    """`ffn(norm(x), identity=x)` of a Swin block in eval mode in one launch.  x [.., C]: fp16 / bf16 on the device, contiguous, of
+    the parameters' dtype; norm: the block's `norm2`, ffn: its `FFN`.  out: a contiguous tensor of x's shape and dtype to write
+    (not x itself), None for a fresh one.  Returns out, or None where the kernel does not serve the modules or the sizes (see
+    `swin_ffn_spec`).  No sync, no host copy; after one call nothing is allocated but out."""
+    if not torch.is_tensor(x) or not x.is_cuda:
+        raise RuntimeError("swin_ffn needs GPU tensors (host tensors: the module's torch layers)")
+    if not _ffn_modules_served(norm, ffn):
+        return None
+    return _swin_ffn_served(x, norm, ffn, out)
+
+
+def _swin_ffn_served(x, norm, ffn, out=None):
+    """`swin_ffn` for modules whose structure the caller has checked (`SwinBlock.forward`, through `swin_ffn_spec`)."""
+    if x.dim() < 1 or x.dtype not in _DTYPES or not x.is_contiguous():
+        raise RuntimeError(f"x must be a contiguous float16 or bfloat16 [.., C], got {tuple(x.shape)} {x.dtype}")
+    fc1, _ = _ffn_linears(ffn)
+    C, hidden = fc1.in_features, fc1.out_features
+    if x.shape[-1] != C or fc1.weight.dtype != x.dtype or fc1.weight.device != x.device or norm.weight.dtype != x.dtype \
+            or norm.weight.device != x.device:
+        raise RuntimeError(f"x {tuple(x.shape)} {x.dtype} on {x.device} does not match the modules ({C} channels, "
+                           f"{fc1.weight.dtype} on {fc1.weight.device})")
+    fold = fold_swin_ffn(norm, ffn)
+    if fold is None:
+        return None
+    if out is None:
+        out = torch.empty_like(x)
+    elif not torch.is_tensor(out) or out.device != x.device or out.dtype != x.dtype or out.shape != x.shape or not out.is_contiguous():
+        raise RuntimeError(f"out must be a contiguous {tuple(x.shape)} of x's dtype and device")
+    p1, p2, gamma, beta, b1, b2 = fold
+    x = x.detach()
+    with torch.cuda.device(x.device):
+        rc = _capi.load().bevamd_swin_ffn_forward(
+            _capi.ptr(x), x.numel(), _capi.ptr(gamma), gamma.numel(), _capi.ptr(beta), beta.numel(), _capi.ptr(p1), p1.numel(),
+            _capi.ptr(b1), b1.numel(), _capi.ptr(p2), p2.numel(), _capi.ptr(b2), b2.numel(), _DTYPES[x.dtype], x.numel() // C, C, hidden,
+            float(norm.eps), _capi.ptr(out), out.numel(), _capi.stream_ptr(x.device))
+    if rc == _UNSUPPORTED:
+        return None
+    _capi.check(rc, "swin_ffn_forward")
+    return out
 
 
 # ---- mmdet's swin_converter ------------------------------------------------------------------------------------------------------

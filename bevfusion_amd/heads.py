@@ -35,8 +35,10 @@ mmdet3d/core/bbox/coders/transfusion_bbox_coder.py, mmdet3d/core/post_processing
     Bottleneck tail (conv3 + BatchNorm + residual + ReLU) and stem (conv 7x7 + BatchNorm + ReLU + MaxPool) for eval mode,
     re-exported from `cam_resnet`;
   * `SwinTransformer`, `SwinBlockSequence`, `SwinBlock`, `ShiftWindowMSA`, `WindowMSA`, `PatchEmbed`, `PatchMerging`, `SwinFFN`
-    (mmcv's FFN, `cam_swin.FFN`; `heads.FFN` stays the TransFusion head's), `DropPath`, `window_attention`, `fold_window_bias`, `window_attention_spec`, `swin_convert`: the camera backbone of the Swin-T
-    configs as a module and its fused shifted-window attention for eval mode, re-exported from `cam_swin`.
+    (mmcv's FFN, `cam_swin.FFN`; `heads.FFN` stays the TransFusion head's), `DropPath`, `window_attention`, `fold_window_bias`, `window_attention_spec`, `swin_convert`, `swin_ffn`,
+    `fold_swin_ffn`, `swin_ffn_spec`, `swin_pack_ffn`: the camera backbone of the Swin-T configs as a module, its fused
+    shifted-window attention and its fused block FFN (LayerNorm, fc1, GELU, fc2, residual) for eval mode, re-exported from
+    `cam_swin`.
 
 Dispatch: device tensors go through the library or raise (no torch formulation for them); host tensors run the reference's
 formulation written in torch / numpy with a STABLE descending argsort, which is the order the kernels are defined to produce
@@ -59,8 +61,8 @@ from .bev_resnet import (BasicBlock, FoldedResBlock, GeneralizedResNet, fold_res
 from .cam_resnet import (Bottleneck, FoldedBottleneckTail, FoldedStem, ResNet, bottleneck_spec, bottleneck_tail_forward,  # noqa: F401
                          fold_bottleneck, fold_stem, stem_forward, stem_pack_weight, stem_spec, stem_unpack_weight)  # (the camera ResNet)
 from .cam_swin import (DropPath, PatchEmbed, PatchMerging, ShiftWindowMSA, SwinBlock, SwinBlockSequence, SwinFFN,  # noqa: F401
-                       SwinTransformer, WindowMSA, fold_window_bias, swin_convert, window_attention,
-                       window_attention_spec)                               # (the camera Swin Transformer)
+                       SwinTransformer, WindowMSA, fold_swin_ffn, fold_window_bias, swin_convert, swin_ffn, swin_ffn_spec,
+                       swin_pack_ffn, window_attention, window_attention_spec)  # (the camera Swin Transformer)
 from .cam_nets import (DepthHeadFold, DepthStemFold, depth_head_forward, depth_stem_forward, fold_conv_bias_bn,  # noqa: F401
                        fold_depth_head, fold_depth_stem)                    # (the camera depth nets)
 from .cam_neck import (LSSFPN, GeneralizedLSSFPN, cam_neck_conv_forward, fold_conv_bias, fold_neck_layer,  # noqa: F401
@@ -94,7 +96,8 @@ __all__ = ["circle_nms", "circle_nms_segments", "TransFusionBBoxCoder", "Proposa
            "ResNet", "Bottleneck", "FoldedBottleneckTail", "FoldedStem", "bottleneck_spec", "fold_bottleneck", "bottleneck_tail_forward",
            "stem_spec", "fold_stem", "stem_forward", "stem_pack_weight", "stem_unpack_weight",
            "SwinTransformer", "SwinBlockSequence", "SwinBlock", "ShiftWindowMSA", "WindowMSA", "PatchEmbed", "PatchMerging", "SwinFFN",
-           "DropPath", "window_attention", "fold_window_bias", "window_attention_spec", "swin_convert"]
+           "DropPath", "window_attention", "fold_window_bias", "window_attention_spec", "swin_convert", "swin_ffn", "fold_swin_ffn",
+           "swin_ffn_spec", "swin_pack_ffn"]
 
 MAX_PROPOSALS = 1024     # HE_MAX_K of the kernels: proposals per sample, rows per NMS segment
 _UNSUPPORTED = 4

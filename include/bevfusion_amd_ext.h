@@ -377,6 +377,41 @@ int bevamd_window_attention_forward(const void* qkv, long long qkv_elems, const 
                                     int window, int head_dim, float scale, int shift, void* out, long long out_elems, void* stream);
 
 
+/* The FFN half of a Swin block in eval mode (mmdet 2.x mmdet/models/backbones/swin.py SwinBlock.forward, `self.ffn(self.norm2(x),
+ * identity=x)` over mmcv's FFN): LayerNorm, Linear C -> hidden, GELU (the erf form), Linear hidden -> C and the residual in ONE
+ * launch on 16-bit storage (dtype 0: fp16, 1: bf16) with fp32 accumulation on v_mfma_f32_16x16x32; the hidden activations never
+ * reach memory; no workspace, no device synchronisation, no atomics, no split-K: equal calls give bit-equal results, a token's
+ * result does not depend on the tokens around it, and the call can be captured in a graph.
+ *
+ * bevamd_swin_ffn_forward: x [tokens, channels] contiguous, 16-byte aligned (x_elems elements).  gamma, beta [channels], b1
+ *   [hidden], b2 [channels]: fp32, 16-byte aligned (the module's 16-bit parameters widened, which is exact).  Per row, in fp32
+ *   without contraction, C = channels:
+ *     mean = (sum_c x_c) / C     var = (sum_c (x_c - mean)^2) / C     rstd = 1 / sqrt(var + eps)        (two passes, c ascending)
+ *     n_c  = round16(fma((x_c - mean) * rstd, gamma_c, beta_c))
+ *     h_j  = round16(gelu(sum_c W1[j][c] n_c + b1_j))       gelu(t) = 0.5 t (1 + erf(t / sqrt 2))
+ *     out_c = round16(x_c + (sum_j W2[c][j] h_j + b2_c))
+ *   Each sum is ONE accumulator chain: the first in ascending k-steps of 32 channels, the second in ascending k-steps of 32 hidden
+ *   units.  1 + erf is evaluated branch-free with an absolute error below 3e-7 (Abramowitz & Stegun 7.1.26 on the hardware
+ *   reciprocal and exp2; csrc/ext/swin_ffn.hip), far below the rounding of h that follows.
+ *   packed1, packed2: W1 [hidden, channels] and W2 [channels, hidden] in MFMA fragment order, 16-byte aligned, hidden * channels
+ *   16-bit elements each (packed1_elems, packed2_elems).  With KS = channels / 32, CT = channels / 16, lane 0 .. 63, e 0 .. 7:
+ *     packed1[((tile * KS + ks) * 64 + lane) * 8 + e] = W1[16 tile + (lane & 15)][32 ks + 8 (lane >> 4) + e]        tile < hidden / 16
+ *     packed2[((s * CT + ct) * 64 + lane) * 8 + e]    = W2[16 ct + (lane & 15)][32 s + 16 (e >> 2) + 4 (lane >> 4) + (e & 3)]
+ *                                                                                                  s < hidden / 32, ct < CT
+ *   (the k order inside a step of packed2 is the order in which a lane holds the hidden units in the first product's result).
+ *   out [tokens, channels] (out_elems elements), 16-byte aligned: every element is written, nothing else, and x is only read
+ *   inside its extent.  out must not overlap x or any other operand.
+ *   Limits, checked on the host before any GPU work, anything else returns 4 (unsupported) with the offending size in the error
+ *   text: channels a multiple of 32 from 32 to 192, hidden a multiple of 32 from 32 to 768.  tokens 0 .. 2^34 (0: nothing to do, x
+ *   and out may be null).  Code 1: a null or misaligned pointer, a bad dtype, an eps that is not finite and positive, element
+ *   counts that do not fit, an overlap.  The entry cannot tell a host pointer from a device pointer (the Python wrapper refuses
+ *   host tensors). */
+int bevamd_swin_ffn_forward(const void* x, long long x_elems, const float* gamma, long long gamma_elems, const float* beta,
+                            long long beta_elems, const void* packed1, long long packed1_elems, const float* b1, long long b1_elems,
+                            const void* packed2, long long packed2_elems, const float* b2, long long b2_elems, int dtype,
+                            long long tokens, int channels, int hidden, float eps, void* out, long long out_elems, void* stream);
+
+
 /* One layer of the camera necks in eval mode (mmdet3d/models/necks/generalized_lss.py GeneralizedLSSFPN, models/necks/lss.py
  * LSSFPN): F.interpolate(bilinear, align_corners=True) + torch.cat + convolution + folded BatchNorm + optional ReLU in ONE launch
  * on 16-bit storage (dtype 0: fp16, 1: bf16) with fp32 accumulation on v_mfma_f32_16x16x32; no workspace, no device

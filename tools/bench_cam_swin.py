@@ -8,13 +8,21 @@
   nets        the whole Swin-T: "fused" (the module's default `fused_stages`), "fused_all" (every stage) and "torch"
               (`use_fused = False`) on the same module in the same session.
 
+  ffn         the tail of a block of each stage the fused FFN serves, on ONE token tensor [B, H W, C]: "fused" is one
+              launch of `bevamd_swin_ffn_forward`, "torch" the module's own `ffn(norm2(x), identity=x)`.  Moved bytes (x in, out out,
+              the two weights once) over the HBM rate are printed as the fused op's floor.
+  ffn_nets    the whole Swin-T under `use_fused = True`: "base" (`fused_ffn_stages = ()`), "ffn0" ((0,)) and "ffn01" ((0, 1)).
+
+`--steps ffn ffn_nets --json profiles/swin_ffn_timing.json` writes the FFN measurement; without `--steps` the run is attention + nets.
+
 Device events around `--iters` calls after `--warmup` calls, the paths alternating inside every round; the median round is reported
 with the spread.
 
 Every step runs in a child process of its own under `timeout`; a step that fails, faults or runs out of time ends the run and
 nothing further is started on the GPU.
 
-    python tools/bench_cam_swin.py [--iters 20] [--warmup 3] [--rounds 5] [--frames 1 8] [--json profiles/cam_swin_timing.json]
+    python tools/bench_cam_swin.py [--steps attention nets] [--iters 20] [--warmup 3] [--rounds 5] [--frames 1 8]
+                                   [--json profiles/cam_swin_timing.json]
 """
 import argparse
 import json
@@ -29,7 +37,9 @@ from tools.bench_bev_trunk import compare  # noqa: E402
 
 IMAGE, CAMERAS = (256, 704), 6
 HBM_BYTES_PER_S = 6.29e12
-STEP_SECONDS = {"attention": 400, "nets": 400}
+STEP_SECONDS = {"attention": 400, "nets": 400, "ffn": 300, "ffn_nets": 400}
+DEFAULT_STEPS = ["attention", "nets"]
+FFN_SETTINGS = {"base": (), "ffn0": (0,), "ffn01": (0, 1)}
 STAGES = [((64, 176), 96, 3), ((32, 88), 192, 6), ((16, 44), 384, 12), ((8, 22), 768, 24)]
 ALL_STAGES = (0, 1, 2, 3)
 
@@ -155,7 +165,73 @@ def step_nets(args):
     return out
 
 
-STEPS = {"attention": step_attention, "nets": step_nets}
+def step_ffn(args):
+    import torch
+
+    from bevfusion_amd import cam_swin as cs
+
+    dev = torch.device("cuda:0")
+    out = {}
+    with torch.no_grad():
+        for frames in args.frames:
+            B = frames * CAMERAS
+            for i, ((H, W), C, heads) in enumerate(STAGES):
+                blk = randomise(cs.SwinBlock(C, heads, 4 * C), 40 + i).to(dev).half().eval()
+                if not cs.swin_ffn_spec(blk):
+                    continue
+                x = torch.randn(B, H * W, C, generator=torch.Generator().manual_seed(50 + i)).half().to(dev)
+                paths = {"torch": lambda blk=blk, x=x: blk.ffn(blk.norm2(x), identity=x),
+                         "fused": lambda blk=blk, x=x: cs.swin_ffn(x, blk.norm2, blk.ffn)}
+                ref = paths["torch"]().float()
+                err = float((paths["fused"]().float() - ref).abs().max()) / float(ref.abs().max())
+                assert err < 2e-2, err                  # both paths compute the same tail (fp16 storage)
+                med, spread = compare(paths, args.iters, args.warmup, args.rounds)
+                T = B * H * W
+                moved = 2 * T * C * 2 + 2 * 4 * C * C * 2
+                torch_bytes = T * C * 2 * (2 + 5 + 8 + 5 + 3)          # LN 1 + 1, fc1 1 + 4, GELU 4 + 4, fc2 4 + 1, add 2 + 1 (in units of T C)
+                key = f"frames{frames}/stage{i + 1}"
+                out[key] = dict(ms=med, spread=spread, speedup=med["torch"] / med["fused"], max_rel_diff=err, tokens=T, channels=C,
+                                moved_bytes=moved, hbm_floor_ms=moved / HBM_BYTES_PER_S * 1e3, torch_sequence_bytes=torch_bytes,
+                                flop=4 * T * C * 4 * C)
+                print(f"{key}: {json.dumps(out[key])}", file=sys.stderr, flush=True)
+    return out
+
+
+def step_ffn_nets(args):
+    import torch
+
+    from bevfusion_amd import cam_swin as cs
+
+    dev = torch.device("cuda:0")
+    net = randomise(cs.SwinTransformer(embed_dims=96, depths=[2, 2, 6, 2], num_heads=[3, 6, 12, 24], out_indices=[1, 2, 3],
+                                       drop_path_rate=0.2), 7).to(dev).half().eval()
+    for p in net.parameters():
+        p.requires_grad_(False)
+    out = {"settings": {k: list(v) for k, v in FFN_SETTINGS.items()}, "default_fused_ffn_stages": list(net.fused_ffn_stages)}
+    default = tuple(net.fused_ffn_stages)
+    with torch.no_grad():
+        for frames in args.frames:
+            x = torch.randn((frames * CAMERAS, 3) + IMAGE, generator=torch.Generator().manual_seed(30 + frames)).half().to(dev)
+
+            def path(stages, x=x):
+                def fn():
+                    net.use_fused, net.fused_ffn_stages = True, stages
+                    return net(x)
+                return fn
+            paths = {k: path(v) for k, v in FFN_SETTINGS.items()}
+            assert net.fusable(x)
+            ref = paths["base"]()[-1].float()
+            errs = {k: float((fn()[-1].float() - ref).abs().max()) / float(ref.abs().max()) for k, fn in paths.items()}
+            assert max(errs.values()) < 5e-2, errs
+            med, spread = compare(paths, args.iters, args.warmup, args.rounds)
+            net.fused_ffn_stages = default
+            out[f"frames{frames}"] = dict(ms=med, spread=spread, speedup={k: med["base"] / v for k, v in med.items() if k != "base"},
+                                          max_rel_diff=errs)
+            print(f"frames{frames}: {json.dumps(out[f'frames{frames}'])}", file=sys.stderr, flush=True)
+    return out
+
+
+STEPS = {"attention": step_attention, "nets": step_nets, "ffn": step_ffn, "ffn_nets": step_ffn_nets}
 
 
 def main():
@@ -165,6 +241,7 @@ def main():
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--frames", type=int, nargs="+", default=[1, 8])
     ap.add_argument("--json", default=None)
+    ap.add_argument("--steps", nargs="+", choices=sorted(STEPS), default=DEFAULT_STEPS, help="the steps to run, each in a child process")
     ap.add_argument("--step", choices=sorted(STEPS), default=None, help="run one step in this process (what the parent starts)")
     args = ap.parse_args()
     if args.step:
@@ -175,7 +252,8 @@ def main():
         print("RESULT " + json.dumps(STEPS[args.step](args)), flush=True)
         return
     results = {}
-    for step, seconds in STEP_SECONDS.items():
+    for step in args.steps:
+        seconds = STEP_SECONDS[step]
         cmd = ["timeout", "-k", "10", str(seconds), sys.executable, os.path.abspath(__file__), "--step", step, "--iters", str(args.iters),
                "--warmup", str(args.warmup), "--rounds", str(args.rounds), "--frames"] + [str(f) for f in args.frames]
         r = subprocess.run(cmd, capture_output=True, text=True)
